@@ -9,7 +9,10 @@ tests/golden/trained_crisp_64_32.npz weights; fp16x3 split MFMA kernel gru16p_ke
 device error count.  K steps are timed between barrier + synchronize; HIP events on the launch stream time every SC
 and GRU launch inside the timed region (the roofline's launch durations).
 
-Other configurations run as sub-records (same weak-scaling rules; every leg decodes its own codeword shard per rank,
+A plain run does only that: set up, warm up, time the K steps, write --dump-outputs if asked, print the result line.
+Everything below runs behind --full.
+
+Other configurations run as sub-records under --full (same weak-scaling rules; every leg decodes its own codeword shard per rank,
 timed between barriers, max over ranks; whole-job codewords/s):
   configs1_sc     configs[1]: SC decode alone (the SC half of the step, HBM-bound) + its PMC traffic
   montecarlo      the fused Monte-Carlo step: Philox message -> encode -> AWGN -> SC -> count, y never stored
@@ -19,14 +22,18 @@ timed between barriers, max over ranks; whole-job codewords/s):
   conv_model      configs[4]: Polar(256,128) convNet (embed 128), fp16x3 split MFMA (fp32 path beside)
   scl, sc_lse     SC-List (run_models.py:329) and exact-LSE SC (polar.py:209-279)
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
   --gpus N > 1 without a launcher: bench.py starts `python -m torch.distributed.run --nproc-per-node N`
   on itself (the parent never touches the GPU) and exits with its status.  Under a launcher,
   WORLD_SIZE must equal --gpus.
 
-Rank 0 writes the full record (every leg) to --full-json and prints ONE compact JSON line last (the headline, its
-roofline and cpu_baseline, and one summary per configuration).  cpu_baseline times the CPU oracle (oracle/: C
+Rank 0 prints ONE compact JSON line last: the headline and the roofline of its timed launches.  With --full it also
+writes the full record (every leg) to --full-json, and the line carries the PMC traffic, cpu_baseline, the comparison
+with the reference's curve and one summary per configuration.  cpu_baseline times the CPU oracle (oracle/: C
 restatements of sc_decode_new and RNN_decoder.decode) on a bounded sample of the same received words.
+
+--dump-outputs DIR: after the timed steps rank 0 writes what the timed step's caller holds after the last step as
+DIR/<name>.npy (dump_outputs below).  The inputs are Philox words and fixture weights, identical from run to run.
 """
 from __future__ import annotations
 
@@ -137,6 +144,11 @@ def parse():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=1 << 20)
     ap.add_argument("--snrs", type=str, default="0,1,2,3,4")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other configuration, the CPU baselines, the PMC traffic pass and the comparisons "
+                         "with the reference (the --no-* switches below trim that); off: the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (rank 0)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="budget of the CPU-baseline sample")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-gru", action="store_true", help="skip the GRU legs besides the headline (fp32 path, crisp_gru, crisp_gru_f512, pac_gru)")
@@ -869,6 +881,29 @@ def pmc_traffic(args, timeout_s=240):
             {k: {c: v[c] * 1024 for c in v} for k, v in vals.items()})
 
 
+# ------------------------------------------------------------------------------------ outputs
+DUMP_MSG_HAT_BYTES = 32 << 20  # of the 64 MB a dump may take
+
+
+def dump_outputs(out_dir, hat, c_sc, c_gru):
+    """What the caller of the timed step holds after its last step, as float32 / float64 .npy files:
+      sc_msg_hat       (n_snr, rows, K) float32  SC's decoded message bits (+-1) of the last step; all B rows when they
+                                                 fit DUMP_MSG_HAT_BYTES, else a fixed sample (PCG64(SEED), sorted)
+      sc_msg_hat_rows  (rows,) float64           the codeword indices of those rows
+      sc_counts        (n_snr, 2) float64        SC [bit errors, block errors], accumulated over the timed steps
+      gru_counts       (n_snr, 2) float64        the CRISP GRU's, likewise (its decisions are counted in the kernel's
+                                                 epilogue and never stored)"""
+    os.makedirs(out_dir, exist_ok=True)
+    nsnr, B, K = hat.shape
+    rows = min(B, DUMP_MSG_HAT_BYTES // (4 * K * nsnr))
+    idx = np.arange(B) if rows == B else np.sort(np.random.default_rng(SEED).choice(B, rows, replace=False))
+    sample = hat if rows == B else hat[:, torch.from_numpy(idx).to(hat.device)]
+    np.save(os.path.join(out_dir, "sc_msg_hat.npy"), sample.cpu().numpy().astype(np.float32))
+    np.save(os.path.join(out_dir, "sc_msg_hat_rows.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "sc_counts.npy"), c_sc.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(out_dir, "gru_counts.npy"), c_gru.cpu().numpy().astype(np.float64))
+
+
 # ------------------------------------------------------------------------------------ main
 def sc_only_record(code, snrs, B, cw0, world, dev, yall, hat, steps, warmup):
     """configs[1]: the SC half of the step alone -- one npd_sc_decode_mc_sweep launch per step (decode + fused counts
@@ -991,6 +1026,8 @@ def main():
     sc_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in ev]))
     gru_sweep_ms = float(np.mean([e[1].elapsed_time(e[2]) for e in ev]))
     gru_ms = gru_sweep_ms / nsnr  # per 2^20-codeword SNR point
+    if args.dump_outputs and rank == 0:  # this rank's shard, before the counters are summed over ranks
+        dump_outputs(args.dump_outputs, hat, c_sc, c_gru)
     allreduce(c_sc, _sum(), world)
     allreduce(c_gru, _sum(), world)
     csc, cg = c_sc.cpu().numpy(), c_gru.cpu().numpy()
@@ -1033,6 +1070,10 @@ def main():
         "sc_ber": {str(s_): float(csc[i, 0]) / (n_cw * K_CODE) for i, s_ in enumerate(snrs)},
         "sc_bler": {str(s_): float(csc[i, 1]) / n_cw for i, s_ in enumerate(snrs)},
     }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(_round_floats(headline)), flush=True)
+        return 0
     gvr = gru_vs_reference(fix, snrs, cg[:, 0], cg[:, 1], n_cw, K_CODE)
     full = {"headline": headline, "gru_vs_reference": gvr}
     ev_tabs = {}

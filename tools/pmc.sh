@@ -3,7 +3,7 @@
 cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out/pmc
 export TMPDIR=/tmp
-ARGS=${BENCH_ARGS:-"--steps 3 --warmup 1 --no-cpu-baseline --no-gru"}
+ARGS=${BENCH_ARGS:-"--full --steps 3 --warmup 1 --no-cpu-baseline --no-gru"}
 [ -n "$LIST" ] && (rocprofv3 -L > gpurun_out/pmc/counters.txt 2>&1; echo "list rc=$?")
 i=0
 for grp in "$@"; do
