@@ -188,6 +188,36 @@ int npd_sc_mc_sweep_fused(const npd_code* code, int n_snr, const float* sigma, c
                           uint32_t snr_index0, uint64_t seed, uint64_t cw_offset, int64_t B, float* msg_hat,
                           unsigned long long* counters, void* stream);
 
+/* ---------------------------------------------------------------------------------- ML / bitwise MAP */
+/*
+ * Decoding against the whole codebook, the "ML" and "bitML" curves of the reference's eval loops
+ * (run_models.py:347-361 and :1374-1377; rnn_all.py:892-948 under --run_ML).  Stateless on an npd_code: the codebook is
+ * never stored -- the kernels XOR K generator rows (computed on the host inside the call) into the sign bits of
+ * fp16 MFMA fragments.  Polar and PAC codes, N in {8, 16, 32, 64}; ML 1 <= K <= 22, MAP 1 <= K <= 16; anything else
+ * returns NPD_ENOTSUP (npd_ml_supported tells beforehand: 1 / 0, < 0 on NULL; map != 0 asks for npd_map_decode).
+ *
+ * Codeword index i follows dec2bitarray (utils.py:170-192), MSB first: message column k of index i is
+ * 1 - 2 * ((i >> (K-1-k)) & 1), so index 0 is the all-(+1) message and all_message_bits[i] (run_models.py:1349-1356)
+ * is row i of the codebook's messages.
+ *
+ * npd_ml_decode: idx[b] = argmax_i sum_j y[b][j] c_i[j], which is the reference's
+ *   diff = (b_noisy - b_codebook).pow(2).sum(2); idx = diff.argmin(1); decoded = all_message_bits[idx]
+ *   (run_models.py:348-351).  Outputs, each optional but at least one: msg_hat (B,K) = all_message_bits[idx],
+ *   idx (B) int32, metric (B) = the chosen codeword's correlation (re-summed in fp64, rounded once).
+ *   Among codewords whose computed correlations are equal and maximal the smallest index wins (torch.argmin's first
+ *   occurrence).  The correlations are sums of exact products (y split into three fp16 planes) accumulated in fp32:
+ *   the chosen codeword's exact correlation is within 2 N 2^-24 sum_j |y_j| of the best one.
+ * npd_map_decode: PolarCode.bitwise_MAP (polar.py:879-899) -- with a = llr_scale * y (llr_scale = 2/sigma^2 >= 0),
+ *   llr[b][k] = logsumexp_{i: bit_k(i) = 0} a.c_i - logsumexp_{i: bit_k(i) = 1} a.c_i and
+ *   msg_hat[b][k] = +1 if llr >= 0 else -1 (torch.max's first index on a tie).  Outputs msg_hat (B,K) and llr (B,K),
+ *   each optional but at least one.  Defined for PAC codes in the same way (the reference has no PAC bitwise_MAP).
+ */
+int npd_ml_supported(const npd_code* code, int map);
+int npd_ml_decode(const npd_code* code, const float* y, float* msg_hat, int32_t* idx, float* metric, int64_t B,
+                  void* stream);
+int npd_map_decode(const npd_code* code, const float* y, float llr_scale, float* msg_hat, float* llr, int64_t B,
+                   void* stream);
+
 /* ---------------------------------------------------------------------------------- counters */
 /*
  * counters[0] += #(round(ref) != round(hat)), counters[1] += #rows with any such element, over

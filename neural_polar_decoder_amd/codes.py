@@ -112,3 +112,66 @@ def pac_default_g(N: int) -> int:
     """The PAC convolution polynomial the reference's scripts use for length N: rnn_all.py:218-235, run_models.py:197-213
     and rnn.py:224-240 overwrite --g from N (7, 13, 21, 53 at N = 4, 8, 16, 32; 91 otherwise)."""
     return {4: 7, 8: 13, 16: 21, 32: 53}.get(int(N), 91)
+
+
+# ------------------------------------------------------------------------------------------- ML / bitwise-MAP codebook
+def all_message_bits(K: int) -> np.ndarray:
+    """The (2^K, K) +-1 message table of the reference's ML block (run_models.py:1349-1354): row i is
+    1 - 2 * dec2bitarray(i, K) (utils.py:170-192, MSB first), so column k of row i is 1 - 2 * ((i >> (K-1-k)) & 1)
+    and row 0 is the all-(+1) message.  ``ml_decode``'s index is a row of this table."""
+    i = np.arange(1 << int(K), dtype=np.int64)[:, None]
+    return (1 - 2 * ((i >> np.arange(int(K) - 1, -1, -1, dtype=np.int64)[None, :]) & 1)).astype(np.float32)
+
+
+def generator_rows(N: int, info, pac_g: int = 0) -> np.ndarray:
+    """K generator rows over GF(2) as uint64 sign masks: bit j of row k is set iff position j of the codeword of the
+    message with -1 in column k only is -1.  The code is linear, so the sign mask of codeword i is the XOR of the rows
+    k whose message column is -1, i.e. of rows K-1-b over the set bits b of i (the ML kernels build their codebook
+    tiles this way from the same rows).  Polar: u[info[k]] = 1, then the Plotkin butterfly (polar.py:128-148).  PAC
+    (pac_g != 0): rate profile, convolution u_i = v_i ^ parity(state & taps) with state <- v (pac_code.py:181-208),
+    rate-1 butterfly."""
+    N = int(N)
+    info = np.sort(np.asarray(info, dtype=np.int64))
+    if N > 64:
+        raise ValueError("generator_rows packs a codeword into 64 bits: N <= 64")
+    tap = smask = 0
+    if pac_g:
+        M = int(pac_g).bit_length()
+        for j in range(1, M):              # g_array[j] (MSB first) taps state[j-1]
+            if (int(pac_g) >> (M - 1 - j)) & 1:
+                tap |= 1 << (j - 1)
+        smask = (1 << (M - 1)) - 1
+    rows = np.zeros(len(info), dtype=np.uint64)
+    for k, pos in enumerate(info):
+        v = [1 if i == int(pos) else 0 for i in range(N)]
+        u = list(v)
+        if pac_g:
+            st = 0
+            for i in range(N):
+                u[i] = v[i] ^ (bin(st & tap).count("1") & 1)
+                st = ((st << 1) | v[i]) & smask
+        h = 1
+        while h < N:
+            for i in range(0, N, 2 * h):
+                for j in range(h):
+                    u[i + j] ^= u[i + h + j]
+            h *= 2
+        rows[k] = np.uint64(sum(b << j for j, b in enumerate(u)))
+    return rows
+
+
+def codebook_masks(rows: np.ndarray, lo: int = 0, hi: int | None = None) -> np.ndarray:
+    """Sign masks (uint64) of the codewords of indices lo .. hi-1: XOR of rows[K-1-b] over the set bits b."""
+    K = len(rows)
+    hi = (1 << K) if hi is None else int(hi)
+    i = np.arange(int(lo), hi, dtype=np.int64)
+    m = np.zeros(i.shape, dtype=np.uint64)
+    for b in range(K):
+        m ^= np.where((i >> b) & 1, rows[K - 1 - b], np.uint64(0)).astype(np.uint64)
+    return m
+
+
+def masks_to_pm1(masks: np.ndarray, N: int, dtype=np.float64) -> np.ndarray:
+    """(len(masks), N) +-1 codewords of uint64 sign masks."""
+    bits = (masks[:, None] >> np.arange(int(N), dtype=np.uint64)[None, :]) & np.uint64(1)
+    return (1 - 2 * bits.astype(np.int64)).astype(dtype)

@@ -168,6 +168,41 @@ class LSEMonteCarlo(SCMonteCarlo):
         return MonteCarlo.count_sweep(self, cw_offset, n, counters)
 
 
+class MLMonteCarlo(SCMonteCarlo):
+    """Maximum-likelihood decoding over the whole codebook (the eval loops' ML block, run_models.py:347-359): fused
+    generate with the message kept + npd_ml_decode + device error counting.  Polar and PAC codes with
+    ``code.ml_supported()``."""
+
+    want_map = False
+
+    def __init__(self, code, snrs, total_cw, batch, seed=1234, rank=None, world=None, device=None):
+        super().__init__(code, snrs, total_cw, batch, seed, rank, world, device, fused=False)
+        if not code.ml_supported(map=self.want_map):
+            raise ValueError(f"{type(self).__name__}: ({code.N}, {code.K}) is outside the codebook decoders' range "
+                             "(N in {8, 16, 32, 64}; K <= 22 for ML, K <= 16 for bitwise MAP)")
+
+    def decisions(self, y, snr):
+        return self.code.ml_decode(y)
+
+    def count_batch(self, si, snr, cw_offset, n, counters_row):
+        from .utils import count_errors
+        msg, _, y = self.code.mc_generate(n, snr, self.seed, si, cw_offset, device=self.device, want_msg=True)
+        count_errors(msg, self.decisions(y, snr), counters_row)
+
+    def count_sweep(self, cw_offset, n, counters):
+        return MonteCarlo.count_sweep(self, cw_offset, n, counters)
+
+
+class MAPMonteCarlo(MLMonteCarlo):
+    """Bitwise-MAP decoding (PolarCode.bitwise_MAP, polar.py:879-899; run_models.py:352-361): fused generate +
+    npd_map_decode + device error counting."""
+
+    want_map = True
+
+    def decisions(self, y, snr):
+        return self.code.bitwise_MAP(y, y.device, snr)
+
+
 class DecoderMonteCarlo(MonteCarlo):
     """A neural decoder's Monte-Carlo: fused generation (npd_mc_generate, message kept), the decoder's
     (n, N) decisions, and decisions[:, info] counted against the message on the device
@@ -256,8 +291,8 @@ def seeded_conv(N, embed_dim=128, seed=0, device="cuda"):
 
 
 def _main(argv=None):
-    ap = argparse.ArgumentParser(description="MI355X BER/BLER Monte-Carlo (SC, SC-List, exact-LSE SC, CRISP GRU, "
-                                             "convNet decoders)")
+    ap = argparse.ArgumentParser(description="MI355X BER/BLER Monte-Carlo (SC, SC-List, exact-LSE SC, ML, bitwise MAP, "
+                                             "CRISP GRU, convNet decoders)")
     ap.add_argument("--code", choices=["polar", "pac"], default="polar")
     ap.add_argument("--N", type=int, default=64)
     ap.add_argument("--K", type=int, default=32)
@@ -274,6 +309,10 @@ def _main(argv=None):
     ap.add_argument("--list_size", type=int, default=None, help="also run SC-List with this list size (Polar)")
     ap.add_argument("--lse", action="store_true", help="also run the exact-LSE sc_decode (Polar, polar.py:209)")
     ap.add_argument("--hard_decision", action="store_true", help="exact-LSE SC with sign decisions (else tanh)")
+    ap.add_argument("--ml", action="store_true", help="also run maximum-likelihood decoding over the codebook "
+                                                      "(run_models.py:347-351; N <= 64, K <= 22)")
+    ap.add_argument("--bitwise_map", action="store_true", help="also run bitwise-MAP decoding (polar.py:879; N <= 64, "
+                                                               "K <= 16)")
     ap.add_argument("--crisp", action="store_true", help="also run the CRISP GRU decoder (rnn_all.py:874)")
     ap.add_argument("--crisp_checkpoint", default=None, help="rnn_all.py checkpoint ({'net', 'args'}) for --crisp")
     ap.add_argument("--rnn_feature_size", type=int, default=64, help="--crisp without checkpoint: hidden size")
@@ -312,6 +351,15 @@ def _main(argv=None):
         if a.code != "polar":
             raise SystemExit("--lse: the exact-LSE sc_decode is defined for Polar codes only (polar.py:209)")
         lse = LSEMonteCarlo(code, snrs, a.test_size, a.batch_size, a.seed, hard_decision=a.hard_decision).run()
+    ml = bmap = None
+    if a.ml:
+        if not code.ml_supported():
+            raise SystemExit("--ml: the codebook sweep covers N in {8, 16, 32, 64} with K <= 22")
+        ml = MLMonteCarlo(code, snrs, a.test_size, a.batch_size, a.seed).run()
+    if a.bitwise_map:
+        if not code.ml_supported(map=True):
+            raise SystemExit("--bitwise_map: bitwise MAP covers N in {8, 16, 32, 64} with K <= 16")
+        bmap = MAPMonteCarlo(code, snrs, a.test_size, a.batch_size, a.seed).run()
     crisp = None
     if a.crisp:
         if a.crisp_checkpoint:
@@ -356,6 +404,14 @@ def _main(argv=None):
             print("BERs of exact-LSE SC decoding: {0}".format(lse.ber))
             print("BLERs of exact-LSE SC decoding: {0}".format(lse.bler))
             rec["sc_lse"] = dict(lse.as_dict(), hard_decision=a.hard_decision)
+        if ml is not None:
+            print("BERs of ML: {0}".format(ml.ber))
+            print("BLERs of ML: {0}".format(ml.bler))
+            rec["ml"] = ml.as_dict()
+        if bmap is not None:
+            print("BERs of bitML: {0}".format(bmap.ber))
+            print("BLERs of bitML: {0}".format(bmap.bler))
+            rec["bitwise_map"] = bmap.as_dict()
         if crisp is not None:
             print("BLERs of RNN: {0}".format(crisp.bler))
             rec["crisp_gru"] = crisp.as_dict()

@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import polar as _ml
 from .codes import pac_info_positions
 from .polar import _aligned, _CodeHandle, _Philox
 import ctypes
@@ -134,6 +135,23 @@ class PAC:
         if B is None:
             B = self.B
         return v_hat[:, torch.as_tensor(np.asarray(B), device=v_hat.device)]
+
+    # ------------------------------------------------------------------ ML / bitwise MAP
+    def ml_supported(self, map=False) -> bool:
+        """Whether ml_decode (or, with ``map=True``, bitwise_MAP) covers this code: N in {8, 16, 32, 64} and
+        K <= 22 (ML) / K <= 16 (MAP)."""
+        return _ml.ml_supported(self._code_for(self.B), map)
+
+    def ml_decode(self, y, return_idx=False):
+        """Maximum-likelihood decoding over the PAC codebook (PAC_MAP_decode, run_models.py:373-381 /
+        rnn_all.py:666-674): all_message_bits[idx] (B,K) with idx = argmin_i ||y - pac_encode(all_message_bits)_i||^2
+        (and idx, int32, with ``return_idx=True``)."""
+        return _ml.ml_decode(self._code_for(self.B), y, return_idx)
+
+    def bitwise_MAP(self, noisy_enc, device=None, snr=0.0, return_llr=False):
+        """Per-bit MAP decisions (B,K) over the PAC codebook, defined as PolarCode.bitwise_MAP (polar.py:879-899) with
+        pac_encode in place of encode_plotkin; ``return_llr=True`` also returns the bit LLRs."""
+        return _ml.map_decode(self._code_for(self.B), noisy_enc, snr, return_llr)
 
     # ------------------------------------------------------------------ Monte-Carlo extras
     def mc_generate(self, Bn, snr, seed, snr_index=0, cw_offset=0, device=None, want_msg=True, want_x=False, out=None):

@@ -276,6 +276,24 @@ class PolarCode:
         hat = _lib.home(hat, corrupted_codewords)
         return (hat, _lib.home(u, corrupted_codewords)) if return_u_hat else hat
 
+    # ------------------------------------------------------------------ ML / bitwise MAP
+    def ml_supported(self, map=False) -> bool:
+        """Whether ml_decode (or, with ``map=True``, bitwise_MAP) covers this code: N in {8, 16, 32, 64} and
+        K <= 22 (ML) / K <= 16 (MAP)."""
+        return ml_supported(self.code, map)
+
+    def ml_decode(self, y, return_idx=False):
+        """Maximum-likelihood decoding, the eval loops' inline ML block (run_models.py:348-351): returns
+        all_message_bits[idx] (B,K) with idx = argmin_i ||y - c_i||^2 (and idx itself, int32, with
+        ``return_idx=True``)."""
+        return ml_decode(self.code, y, return_idx)
+
+    def bitwise_MAP(self, noisy_enc, device=None, snr=0.0, return_llr=False):
+        """PolarCode.bitwise_MAP(noisy_enc, device, snr) (polar.py:879-899): per-bit MAP decisions (B,K) over the whole
+        codebook; ``return_llr=True`` also returns the bit LLRs.  ``device`` is accepted for the reference's
+        signature; the compute runs on the GPU that holds (or stages) ``noisy_enc``."""
+        return map_decode(self.code, noisy_enc, snr, return_llr)
+
     # ------------------------------------------------------------------ Monte-Carlo extras
     def mc_generate(self, B, snr, seed, snr_index=0, cw_offset=0, device=None, want_msg=True, want_x=False, out=None):
         device = torch.device(device or "cuda") if out is None else out.device
@@ -344,6 +362,46 @@ class PolarCode:
 def _aligned(y: torch.Tensor) -> torch.Tensor:
     """The list kernel reads 16-byte vectors: re-base an unaligned view (rare: odd row offsets)."""
     return y if y.data_ptr() % 16 == 0 else y.clone()
+
+
+def ml_supported(h: _CodeHandle, map=False) -> bool:
+    rc = _lib.load().npd_ml_supported(h.h, 1 if map else 0)
+    if rc < 0:
+        _lib.check(rc, "npd_ml_supported")
+    return bool(rc)
+
+
+def _received(h: _CodeHandle, y, name):
+    y = _lib.f32c(_lib.stage(y, name))
+    if y.dim() != 2 or y.shape[1] != h.N:
+        raise ValueError(f"{name} must be (batch, {h.N}), got {tuple(y.shape)}")
+    return y
+
+
+def ml_decode(h: _CodeHandle, y_in, return_idx=False, return_metric=False):
+    """npd_ml_decode on a code handle (shared by PolarCode and PAC): msg_hat (B,K) [, idx (B) int32]
+    [, metric (B) = the chosen codeword's correlation]."""
+    y = _received(h, y_in, "y")
+    B = y.shape[0]
+    hat = torch.empty(B, h.K, dtype=torch.float32, device=y.device)
+    idx = torch.empty(B, dtype=torch.int32, device=y.device) if return_idx else None
+    met = torch.empty(B, dtype=torch.float32, device=y.device) if return_metric else None
+    _lib.check(_lib.load().npd_ml_decode(h.h, _lib.ptr(y), _lib.ptr(hat), _lib.ptr(idx), _lib.ptr(met), B,
+                                         _lib.stream_of(y.device)), "npd_ml_decode")
+    out = (_lib.home(hat, y_in),) + ((_lib.home(idx, y_in),) if return_idx else ()) + \
+        ((_lib.home(met, y_in),) if return_metric else ())
+    return out[0] if len(out) == 1 else out
+
+
+def map_decode(h: _CodeHandle, y_in, snr, return_llr=False):
+    """npd_map_decode on a code handle: decisions (B,K) [, llr (B,K)] at llr_scale = 2 / sigma(snr)^2."""
+    y = _received(h, y_in, "noisy_enc")
+    B = y.shape[0]
+    hat = torch.empty(B, h.K, dtype=torch.float32, device=y.device)
+    llr = torch.empty(B, h.K, dtype=torch.float32, device=y.device) if return_llr else None
+    _lib.check(_lib.load().npd_map_decode(h.h, _lib.ptr(y), llr_scale(snr), _lib.ptr(hat), _lib.ptr(llr), B,
+                                          _lib.stream_of(y.device)), "npd_map_decode")
+    return (_lib.home(hat, y_in), _lib.home(llr, y_in)) if return_llr else _lib.home(hat, y_in)
 
 
 def reference_polar_code(N: int, K: int, args=None, infty=1000.) -> PolarCode:
