@@ -317,6 +317,34 @@ int npd_gru_decode_count_sweep(const npd_gru* gru, int n_seg, const float* y, co
                                const float* msg, int K, const int32_t* cols, float* decoded, int64_t B,
                                unsigned long long* counters, void* stream);
 /*
+ * CRISP GRU list decoding, RNN_decoder.list_decode(net, y, code, L) (rnn_all.py:563-664, decoding_type y_input) with
+ * its pruneLists (rnn_all.py:563-578): list_size partial decodings per word; every live path runs one GRU step per
+ * position on [fy, onehot(its previous bit)] (+1 at step 0 and after a frozen position); a frozen position only
+ * advances the state (bit +1, no metric penalty, unlike SCL); an information position forks each path into
+ * sign(out) (metric unchanged) and -sign(out) (metric + |out|, fp32 in step order), both on the same new state, and
+ * when more than list_size children exist the survivors are torch.topk's choice (ties resolved exactly as
+ * std::nth_element, see npd_list_prune_select; a NaN metric ranks as topk ranks it) in ascending child order.  The
+ * final path is the first minimum over the list of ||encode(msg) - y||^2 with the code's own encoder (Polar: Plotkin
+ * transform; PAC: rate-1 convolution, then the transform).
+ * y (B,N): the received words, used for the final selection; fy (B,N): the GRU's input, or NULL to use y (nets with a
+ * y-MLP pass its output, RNN_Model.get_Fy); both 16-byte aligned.  The information set and the encoder come from
+ * `code` (Polar or PAC), whose N must equal the handle's.  1 <= list_size <= 8 (any value, not only powers of two);
+ * there are min(list_size, 2^K) survivors.
+ * Outputs, each optional but at least one of msg_hat and cand_msg: msg_hat (B,K) the chosen survivor's message (+-1),
+ * sel (B) int32 its index in list order, cand_msg (B, list_size, K) and cand_metric (B, list_size) the final list in
+ * the reference's order; unused slots (2^K < list_size) carry metric +inf and message 0.
+ * One launch, no allocation, no host synchronisation; B = 0 returns NPD_OK.  Runs on the fp32 LDS-resident kernel:
+ * GRU handles with precision 0, F 32 or 64, 1 or 2 layers and the plain Linear(F, 1) head -- LSTM, split-precision,
+ * F >= 128, LayerNorm-head and out_linear_depth > 1 handles return NPD_ENOTSUP (npd_gru_list_supported tells
+ * beforehand: 1 / 0, < 0 on NULL).  list_size = 1 is npd_gru_decode's greedy decision, bit for bit.
+ * Decisions follow the reference's arithmetic in fp32 (gate nonlinearities to ~1 ulp, as npd_gru_decode), so a
+ * survivor set can differ where two metrics are closer than the logits' tolerance, and two candidates whose fp32
+ * distances differ only by summation order (torch's vectorised sum vs the kernel's) may swap in the final selection.
+ */
+int npd_gru_list_supported(const npd_gru* gru, const npd_code* code, int list_size);
+int npd_gru_list_decode(const npd_gru* gru, const npd_code* code, const float* y, const float* fy, int list_size,
+                        float* msg_hat, int32_t* sel, float* cand_msg, float* cand_metric, int64_t B, void* stream);
+/*
  * One layer of RNN_Model.get_h0 / get_Fy (rnn_all.py:362-385): out (B, Nout) = act(x (B, K) W^T + bias), W (Nout, K)
  * row-major, all device fp32, k summed in order.  act: 0 linear, 1 relu, 2 selu, 3 elu, 4 tanh, 5 sigmoid
  * (RNN_Model.act, rnn_all.py:346-360).  get_h0 follows layer ii with act iff ii != y_depth (rnn_all.py:364-368): every

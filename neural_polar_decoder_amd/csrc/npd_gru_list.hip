@@ -1,0 +1,435 @@
+// npd_gru_list.hip -- CRISP GRU list decoder (RNN_decoder.list_decode, y_input).
+//
+// Reference: rnn_all.py:563-664.  L partial decodings per received word stay alive; every live path runs one GRU step
+// per position, forks at an information position into sign(out) (metric unchanged) and -sign(out) (metric + |out|),
+// pruneLists keeps torch.topk(-metric, L) in ascending child order, and the survivor whose re-encoded word is nearest
+// to y (first minimum) is the answer.  Frozen positions only advance the state: bit +1, no metric penalty.
+//
+// MI355X design: gru_decode_kernel's step (npd_gru.hip: weights in LDS, 4 waves, v_mfma_f32_32x32x2_f32, the state
+// tiles are the next step's B operands) with another column map.  With Lp = L rounded up to 1, 2, 4 or 8, a wave's 32
+// MFMA columns are 32 / Lp codewords x Lp path slots, column = cw * Lp + slot; Lp = 1 is gru_decode_kernel's map.
+// Each column carries its path's metric and its N bits as bit words (1 = the bit is -1).
+//
+// While the list fills (2 ls <= L) slot s holds a copy of path s mod ls: all slots of a codeword start from the same
+// y and zero state, so the copies are bit-identical and a fork only flips the bit of the slots whose new path index
+// (s mod 2 ls) is >= ls: nothing moves.  Once 2 ls > L every information step chooses L of the 2 ls children
+// (rank counting; npd_nth.hpp's statement of torch.topk when a tie straddles the L-th place), compacts them in
+// ascending child index and gathers state, bits and metric from the parent column with ds_bpermute_b32 inside the
+// lane half; the gather is skipped when no lane of the wave moves.
+#include <stdlib.h>
+#include <string.h>
+
+#include "npd_gru_common.hpp"
+#include "npd_nth.hpp"
+
+namespace npd {
+namespace gru {
+
+struct ListArgs {
+    const float* img;
+    const f4* wy;
+    const float* y;    // (B, N) received words: final selection
+    const float* fy;   // (B, N) GRU input
+    float* msg_hat;    // (B, K) or NULL
+    int32_t* sel;      // (B) or NULL
+    float* cand_msg;   // (B, L, K) or NULL
+    float* cand_metric;  // (B, L) or NULL
+    int64_t B;
+    int N, K, L, lp_log2;
+    int onehot, pac;
+    float b_lin;
+    uint32_t tapmask, smask;
+    uint32_t info[kMaxWords];
+};
+
+typedef float f8v __attribute__((ext_vector_type(8)));
+
+// metric x beats metric y in pruneLists: torch.topk(-metric) with NaN as the largest value (nth::comp on the negated metrics)
+__device__ __forceinline__ bool beats(float x, float y) { return (x != x && y == y) || (x < y); }
+
+// survivors when a tie straddles the L-th place (rare): the reference's exact rule on the list order
+// [keep_0 .. keep_{s-1}, flip_0 .. flip_{s-1}].  Vectors by value (VGPRs), the queue lives on this function's stack.
+__device__ __noinline__ uint32_t list_exact_mask(f8v km, f8v fm, int s, int L) {
+    float v[16];
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+        v[t] = 0.0f;
+        v[8 + t] = 0.0f;
+    }
+#pragma unroll
+    for (int t = 0; t < 8; ++t)
+        if (t < s) {
+            v[t] = -1.0f * km[t];
+            v[s + t] = -1.0f * fm[t];
+        }
+    return nth::prune_mask(v, 2 * s, L);
+}
+
+template <int F, int L>
+__global__ __launch_bounds__(64 * NPD_GRU_WPB) void gru_list_kernel(const ListArgs a) {
+    constexpr int WPB = NPD_GRU_WPB;
+    using G = Geo<F, L>;
+    constexpr int TT = G::TT, HT = G::HT, KG = G::KG;
+    extern __shared__ __attribute__((aligned(16))) f4 smem4[];
+    const float* smem = reinterpret_cast<const float*>(smem4);
+    {
+        const f4* src = reinterpret_cast<const f4*>(a.img);
+        for (int i = threadIdx.x; i < G::TOTAL / 4; i += blockDim.x) smem4[i] = src[i];
+        __syncthreads();
+    }
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int half = lane >> 5;
+    const int col = lane & 31;
+    const int N = a.N;
+    const int lpl = a.lp_log2, Lp = 1 << lpl;
+    const int slot = col & (Lp - 1);
+    const int base = lane - slot;  // this codeword's slot 0, in this lane half
+    const int cpt = 32 >> lpl;     // codewords per wave tile
+    const uint32_t gmask = (1u << Lp) - 1u;
+    const int64_t ntiles = (a.B + cpt - 1) / cpt;
+    const float kInf = __builtin_inff();
+    const f16v zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    auto cvec = [&](int off) -> f16v {
+        const f4* p = reinterpret_cast<const f4*>(smem + off + half * 16);
+        const f4 x0 = p[0], x1 = p[1], x2 = p[2], x3 = p[3];
+        return f16v{x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3],
+                    x2[0], x2[1], x2[2], x2[3], x3[0], x3[1], x3[2], x3[3]};
+    };
+
+    for (int64_t tile = (int64_t)blockIdx.x * WPB + wave; tile < ntiles; tile += (int64_t)gridDim.x * WPB) {
+        const int64_t cw = tile * cpt + (col >> lpl);
+        const bool valid = cw < a.B;
+        const int64_t cwc = valid ? cw : a.B - 1;
+
+        // ---- P = W_ih0[:, :N] . Fy, once per column (the slots of a codeword compute the same P)
+        f16v P[TT];
+#pragma unroll
+        for (int t = 0; t < TT; ++t) P[t] = zero;
+        {
+            const f4* yr = reinterpret_cast<const f4*>(a.fy + cwc * N + half * (N / 2));
+            const int ng = N / 8;
+            for (int s4 = 0; s4 < ng; ++s4) {
+                const f4 yv = yr[s4];
+#pragma unroll
+                for (int t = 0; t < TT; ++t) {
+                    const f4 w = a.wy[(t * ng + s4) * 64 + lane];
+                    P[t] = mfma(w.x, yv.x, P[t]);
+                    P[t] = mfma(w.y, yv.y, P[t]);
+                    P[t] = mfma(w.z, yv.z, P[t]);
+                    P[t] = mfma(w.w, yv.w, P[t]);
+                }
+            }
+        }
+
+        f16v h0[HT], h1[HT];
+#pragma unroll
+        for (int t = 0; t < HT; ++t) {
+            h0[t] = zero;
+            h1[t] = zero;
+        }
+        float xb = 1.0f;   // x_i of this path: onehot index of its previous bit (or its sign); +1 at step 0 / after frozen
+        float met = 0.0f;  // path metric
+        uint32_t bw[kMaxWords];  // the path's bits, bit i of word i / 32 set = position i decided -1
+#pragma unroll
+        for (int w = 0; w < kMaxWords; ++w) bw[w] = 0u;
+        int ls = 1;  // live list size (the same for every codeword)
+
+        for (int ii = 0; ii < N; ++ii) {
+            const float xbe = half ? xb : 1.0f;  // extra k-step B operand: [1, x_i]
+            // ================= layer 0 (as gru_decode_kernel)
+            {
+                f16v acc[TT];
+#pragma unroll
+                for (int t = 0; t < 2 * HT; ++t) acc[t] = P[t];
+#pragma unroll
+                for (int t = 2 * HT; t < TT; ++t) acc[t] = cvec(G::OFF_CV + (t - 2 * HT) * 32);
+                gemm_chain<TT, KG, TT, HT>(smem4, 0, 0, lane, acc, h0);
+#pragma unroll
+                for (int t = 0; t < 2 * HT; ++t) acc[t] = mfma(smem[G::OFF_X + t * 64 + lane], xbe, acc[t]);
+#pragma unroll
+                for (int j = 0; j < HT; ++j) {
+                    const f16v ain = mfma(smem[G::OFF_IN + j * 64 + lane], xbe, P[2 * HT + j]);
+                    gru_update<true>(h0[j], acc[j], acc[HT + j], ain, acc[2 * HT + j]);
+                }
+            }
+            if constexpr (L == 2) {
+                // ================= layer 1
+                f16v acc1[TT];
+#pragma unroll
+                for (int t = 0; t < TT; ++t) acc1[t] = cvec(G::OFF_CV + (HT + t) * 32);
+                gemm_chain<TT, KG, TT, HT>(smem4, 1, 0, lane, acc1, h0);
+                f16v arz[2 * HT];
+#pragma unroll
+                for (int t = 0; t < 2 * HT; ++t) arz[t] = acc1[t];
+                gemm_chain<TT, KG, 2 * HT, HT>(smem4, 2, 0, lane, arz, h1);
+                f16v ahn[HT];
+#pragma unroll
+                for (int j = 0; j < HT; ++j) ahn[j] = cvec(G::OFF_CV + (HT + TT + j) * 32);
+                gemm_chain<TT, KG, HT, HT>(smem4, 2, 2 * HT, lane, ahn, h1);
+#pragma unroll
+                for (int j = 0; j < HT; ++j) gru_update<true>(h1[j], arz[j], arz[HT + j], acc1[2 * HT + j], ahn[j]);
+            }
+            // ================= output: Linear(F, 1) on the top layer
+            float part = 0.0f;
+#pragma unroll
+            for (int t = 0; t < HT; ++t) {
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const float wl = smem[G::OFF_WL + (half * HT + t) * 16 + i];
+                    part += wl * (L == 2 ? h1[t][i] : h0[t][i]);
+                }
+            }
+            const float out = part + __shfl_xor(part, 32, 64) + a.b_lin;
+
+            const bool info = (a.info[ii >> 5] >> (ii & 31)) & 1u;
+            if (!info) {  // frozen: only the state advances; the bit stays +1
+                xb = 1.0f;
+                continue;
+            }
+            // ================= information position: fork, prune, gather
+            const float ao = fabsf(out);
+            uint32_t neg = out < 0.0f ? 1u : 0u;  // the kept child's bit is sign(out) (an exact 0 counts as +1)
+            bool flip;
+            if (2 * ls <= a.L) {
+                // filling: slot s already holds its parent (path s mod ls); its new path index is s mod 2 ls
+                flip = (slot & (2 * ls - 1)) >= ls;
+                if (flip) met += ao;
+                ls *= 2;
+            } else {
+                // children in list order: c < ls keeps slot c's bit and metric, c >= ls flips slot c - ls's
+                const float mk = met, mf = met + ao;
+                f8v km, fm;
+#pragma unroll
+                for (int t = 0; t < 8; ++t) {
+                    const int sl = base + (t < ls ? t : 0);
+                    km[t] = __shfl(mk, sl, 64);
+                    fm[t] = __shfl(mf, sl, 64);
+                }
+                // rank counting for this slot's two children: nb candidates beat it, ne are equivalent (itself too)
+                int nbk = 0, nek = 0, nbf = 0, nef = 0;
+#pragma unroll
+                for (int t = 0; t < 8; ++t) {
+                    if (t < ls) {
+                        const bool b1 = beats(km[t], mk), e1 = !b1 && !beats(mk, km[t]);
+                        const bool b2 = beats(fm[t], mk), e2 = !b2 && !beats(mk, fm[t]);
+                        const bool b3 = beats(km[t], mf), e3 = !b3 && !beats(mf, km[t]);
+                        const bool b4 = beats(fm[t], mf), e4 = !b4 && !beats(mf, fm[t]);
+                        nbk += (int)b1 + (int)b2;
+                        nek += (int)e1 + (int)e2;
+                        nbf += (int)b3 + (int)b4;
+                        nef += (int)e3 + (int)e4;
+                    }
+                }
+                const bool mine = slot < ls;
+                const bool sk = mine && nbk < a.L, sf = mine && nbf < a.L;
+                // a class of equivalent metrics straddles the L-th place: the top-L set is not unique
+                const bool amb = (sk && nbk + nek > a.L) || (sf && nbf + nef > a.L);
+                const uint64_t bk = __ballot(sk), bf = __ballot(sf), ba = __ballot(amb);
+                uint32_t mask = ((uint32_t)(bk >> base) & gmask) | (((uint32_t)(bf >> base) & gmask) << ls);
+                if (((uint32_t)(ba >> base) & gmask) != 0u) mask = list_exact_mask(km, fm, ls, a.L);
+                // slot j takes the j-th survivor in ascending child index
+                int child = -1, cnt = 0;
+#pragma unroll
+                for (int c = 0; c < 16; ++c) {
+                    const int bit = (int)((mask >> c) & 1u);
+                    if (bit && cnt == slot) child = c;
+                    cnt += bit;
+                }
+                const bool live = slot < a.L && child >= 0;
+                flip = live && child >= ls;
+                const int src = live ? base + (flip ? child - ls : child) : lane;
+                // metric and bit always come from the parent; state and bit words only when some lane of the wave moves
+                const float pk = __shfl(mk, src, 64), pf = __shfl(mf, src, 64);
+                met = flip ? pf : pk;
+                neg = (uint32_t)__shfl((int)neg, src, 64);
+                if (__ballot(src != lane) != 0ull) {
+#pragma unroll
+                    for (int t = 0; t < HT; ++t)
+#pragma unroll
+                        for (int i = 0; i < 16; ++i) {
+                            h0[t][i] = __shfl(h0[t][i], src, 64);
+                            if constexpr (L == 2) h1[t][i] = __shfl(h1[t][i], src, 64);
+                        }
+#pragma unroll
+                    for (int w = 0; w < kMaxWords; ++w)
+                        if (32 * w < N) bw[w] = (uint32_t)__shfl((int)bw[w], src, 64);
+                }
+                ls = a.L;
+            }
+            neg ^= flip ? 1u : 0u;
+#pragma unroll
+            for (int w = 0; w < kMaxWords; ++w) bw[w] |= (w == (ii >> 5)) ? (neg << (ii & 31)) : 0u;
+            xb = a.onehot ? (neg ? 0.0f : 1.0f) : (neg ? -1.0f : 1.0f);
+        }
+
+        // ================= epilogue: encode every path, distance to y, first minimum over the live slots
+        uint32_t cd[kMaxWords];
+#pragma unroll
+        for (int w = 0; w < kMaxWords; ++w) cd[w] = bw[w];
+        if (a.pac) {
+            // rate-1 convolution (encode_kernel, npd_gen.hip): u_i = v_i xor parity(state & taps), state <- v
+            uint32_t st = 0;
+#pragma unroll
+            for (int w = 0; w < kMaxWords; ++w)
+                if (32 * w < N) {
+                    const uint32_t vin = bw[w];
+                    uint32_t uo = 0u;
+                    for (int b = 0; b < 32; ++b) {
+                        const uint32_t vi = (vin >> b) & 1u;
+                        uo |= (vi ^ ((uint32_t)__builtin_popcount(st & a.tapmask) & 1u)) << b;
+                        st = ((st << 1) | vi) & a.smask;
+                    }
+                    const int rem = N - 32 * w;
+                    cd[w] = rem >= 32 ? uo : (uo & ((1u << rem) - 1u));
+                }
+        }
+        // Plotkin butterfly over GF(2): x_i ^= x_{i+h} where bit h of i is clear (words past N are zero)
+        {
+            constexpr uint32_t km[5] = {0x55555555u, 0x33333333u, 0x0F0F0F0Fu, 0x00FF00FFu, 0x0000FFFFu};
+#pragma unroll
+            for (int s = 0; s < 5; ++s)
+#pragma unroll
+                for (int w = 0; w < kMaxWords; ++w) cd[w] ^= (cd[w] >> (1 << s)) & km[s];
+#pragma unroll
+            for (int hw = 1; hw < kMaxWords; hw <<= 1)
+#pragma unroll
+                for (int w = 0; w < kMaxWords; ++w)
+                    if ((w & hw) == 0) cd[w] ^= cd[w + hw];
+        }
+        // fp32 distance: each lane half sums 16 positions of every word
+        float ds = 0.0f;
+        {
+            const float* yrow = a.y + cwc * N;
+#pragma unroll
+            for (int w = 0; w < kMaxWords; ++w)
+                if (32 * w < N) {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const int i0 = 32 * w + 16 * half + 4 * q;
+                        if (i0 < N) {
+                            const f4 yv = *reinterpret_cast<const f4*>(yrow + i0);
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) {
+                                const float c = ((cd[w] >> (16 * half + 4 * q + e)) & 1u) ? -1.0f : 1.0f;
+                                const float d = c - yv[e];
+                                ds = fmaf(d, d, ds);
+                            }
+                        }
+                    }
+                }
+        }
+        const float dist = ds + __shfl_xor(ds, 32, 64);
+        float best = 0.0f;
+        int bsel = 0;
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+            const float dt = __shfl(dist, base + (t < ls ? t : 0), 64);
+            if (t == 0 || (t < ls && dt < best)) {
+                best = t == 0 ? dt : (dt < best ? dt : best);
+                bsel = t;
+            }
+        }
+        if (half == 0 && valid && slot < a.L) {
+            const bool alive = slot < ls;
+            const bool chosen = slot == bsel;
+            if (a.cand_metric) a.cand_metric[cw * a.L + slot] = alive ? met : kInf;
+            if (a.sel && chosen) a.sel[cw] = bsel;
+            float* cm = a.cand_msg ? a.cand_msg + (cw * a.L + slot) * (int64_t)a.K : nullptr;
+            float* mh = (a.msg_hat && chosen) ? a.msg_hat + cw * (int64_t)a.K : nullptr;
+            int k = 0;
+#pragma unroll
+            for (int w = 0; w < kMaxWords; ++w)
+                if (32 * w < N) {
+                    const uint32_t iw = a.info[w], vw = bw[w];
+                    for (int b = 0; b < 32; ++b)
+                        if ((iw >> b) & 1u) {
+                            const float v = ((vw >> b) & 1u) ? -1.0f : 1.0f;
+                            if (cm) cm[k] = alive ? v : 0.0f;
+                            if (mh) mh[k] = v;
+                            ++k;
+                        }
+                }
+        }
+    }
+}
+
+template <int F, int L>
+static int launch_list(const ListArgs& a, hipStream_t s) {
+    using G = Geo<F, L>;
+    constexpr int WPB = NPD_GRU_WPB;
+    auto kern = gru_list_kernel<F, L>;
+    const size_t lds = (size_t)G::TOTAL * 4;
+    static bool attr = false;
+    if (!attr) {
+        NPD_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 163840));
+        attr = true;
+    }
+    const int cpt = 32 >> a.lp_log2;
+    const int64_t tiles = (a.B + cpt - 1) / cpt;
+    const int64_t wgs = (tiles + WPB - 1) / WPB;
+    const int grid = grid_for(wgs, 1, device_cu_count());
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * WPB), lds, s, a);
+    return launch_check("gru_list_kernel launch");
+}
+
+}  // namespace gru
+}  // namespace npd
+
+using namespace npd;
+
+// the handles the list kernel covers: the fp32 LDS-resident GRU kernel's (F 32 or 64, plain Linear head)
+static bool list_handle_ok(const npd_gru* g) {
+    return g->cell == 0 && g->precision == 0 && (g->F == 32 || g->F == 64) && g->ln == 0 && g->hd == nullptr;
+}
+
+extern "C" int npd_gru_list_supported(const npd_gru* gru, const npd_code* code, int list_size) {
+    NPD_ARG(gru != nullptr && code != nullptr, "npd_gru_list_supported: NULL handle");
+    return (list_handle_ok(gru) && code->p.N == gru->N && list_size >= 1 && list_size <= 8) ? 1 : 0;
+}
+
+extern "C" int npd_gru_list_decode(const npd_gru* g, const npd_code* code, const float* y, const float* fy,
+                                   int list_size, float* msg_hat, int32_t* sel, float* cand_msg, float* cand_metric,
+                                   int64_t B, void* stream) {
+    NPD_ARG(g != nullptr, "npd_gru_list_decode: gru is NULL");
+    NPD_ARG(code != nullptr, "npd_gru_list_decode: code is NULL");
+    NPD_ARG(B >= 0, "npd_gru_list_decode: B < 0");
+    NPD_ARG(list_size >= 1 && list_size <= 8, "npd_gru_list_decode: list_size must be 1 .. 8");
+    NPD_ARG(code->p.N == g->N, "npd_gru_list_decode: the code's N differs from the GRU handle's");
+    if (!list_handle_ok(g))
+        return fail(NPD_ENOTSUP, "npd_gru_list_decode: list decoding runs on the fp32 GRU kernel (GRU cell, precision 0, "
+                                 "F 32 or 64, plain Linear head)");
+    if (B == 0) return NPD_OK;
+    NPD_ARG(msg_hat != nullptr || cand_msg != nullptr, "npd_gru_list_decode: msg_hat and cand_msg both NULL");
+    NPD_ARG(y != nullptr, "npd_gru_list_decode: y is NULL");
+    if (fy == nullptr) fy = y;
+    NPD_ARG(((uintptr_t)y & 15) == 0 && ((uintptr_t)fy & 15) == 0, "npd_gru_list_decode: y and fy must be 16-byte aligned");
+    NPD_ARG(B <= (int64_t)1 << 40, "npd_gru_list_decode: B too large");
+    gru::ListArgs a{};
+    a.img = g->img;
+    a.wy = reinterpret_cast<const gru::f4*>(g->wy);
+    a.y = y;
+    a.fy = fy;
+    a.msg_hat = msg_hat;
+    a.sel = sel;
+    a.cand_msg = cand_msg;
+    a.cand_metric = cand_metric;
+    a.B = B;
+    a.N = g->N;
+    a.K = code->p.K;
+    a.L = list_size;
+    a.lp_log2 = list_size <= 1 ? 0 : list_size <= 2 ? 1 : list_size <= 4 ? 2 : 3;
+    a.onehot = g->onehot;
+    a.pac = code->p.pac;
+    a.b_lin = g->b_lin;
+    a.tapmask = code->p.tapmask;
+    a.smask = code->p.smask;
+    for (int w = 0; w < kMaxWords; ++w) a.info[w] = 0;
+    for (int i = 0; i < g->N; ++i)
+        if (!((code->p.frozen[i >> 5] >> (i & 31)) & 1u)) a.info[i >> 5] |= 1u << (i & 31);
+    hipStream_t s = (hipStream_t)stream;
+    if (g->F == 64 && g->layers == 2) return gru::launch_list<64, 2>(a, s);
+    if (g->F == 64) return gru::launch_list<64, 1>(a, s);
+    if (g->layers == 2) return gru::launch_list<32, 2>(a, s);
+    return gru::launch_list<32, 1>(a, s);
+}

@@ -257,6 +257,30 @@ class GRUMonteCarlo(DecoderMonteCarlo):
         self.decoder.decode_count_sweep(self.net, y, msg, counters, cols=self.info_np)
 
 
+class GRUListMonteCarlo(GRUMonteCarlo):
+    """CRISP GRU list decoding (the reference's "RNNL" curve, rnn_all.py:580-664, :866-873): RNN_decoder.list_decode's
+    (n, K) messages counted against the generated ones."""
+
+    def __init__(self, code, net, decoder, list_size, snrs, total_cw, batch, seed=1234, rank=None, world=None,
+                 device=None):
+        super().__init__(code, net, decoder, snrs, total_cw, batch, seed, rank, world, device)
+        if not decoder.list_supported(net, list_size):
+            from ._lib import NpdError
+            raise NpdError(decoder._list_reason(net, list_size))
+        self.list_size = int(list_size)
+
+    def decisions(self, y):
+        return self.decoder.list_decode(self.net, y, self.code, self.list_size)
+
+    def count(self, msg, dec, counters_row):
+        """list_decode returns the K message columns themselves."""
+        from .utils import count_errors
+        count_errors(msg, dec, counters_row)
+
+    def count_sweep(self, cw_offset, n, counters):
+        return MonteCarlo.count_sweep(self, cw_offset, n, counters)
+
+
 class ConvMonteCarlo(DecoderMonteCarlo):
     """convNet decoding (run_models.py:333-337, testXformer): sign of the LayerNorm output at the info
     positions vs the message."""
@@ -290,9 +314,9 @@ def seeded_conv(N, embed_dim=128, seed=0, device="cuda"):
     return convNet(cfg).to(device).eval()
 
 
-def _main(argv=None):
+def _parse_args(argv=None):
     ap = argparse.ArgumentParser(description="MI355X BER/BLER Monte-Carlo (SC, SC-List, exact-LSE SC, ML, bitwise MAP, "
-                                             "CRISP GRU, convNet decoders)")
+                                             "CRISP GRU, CRISP GRU list, convNet decoders)")
     ap.add_argument("--code", choices=["polar", "pac"], default="polar")
     ap.add_argument("--N", type=int, default=64)
     ap.add_argument("--K", type=int, default=32)
@@ -317,11 +341,24 @@ def _main(argv=None):
     ap.add_argument("--crisp_checkpoint", default=None, help="rnn_all.py checkpoint ({'net', 'args'}) for --crisp")
     ap.add_argument("--rnn_feature_size", type=int, default=64, help="--crisp without checkpoint: hidden size")
     ap.add_argument("--rnn_depth", type=int, default=2, help="--crisp without checkpoint: GRU layers")
+    ap.add_argument("--rnn_list_size", type=int, default=None, help="with --crisp: also run the GRU list decoder "
+                                                                    "(RNN_decoder.list_decode, rnn_all.py:580) with this "
+                                                                    "list size (1 .. 8)")
     ap.add_argument("--conv", action="store_true", help="also run the convNet decoder (run_models.py:333)")
     ap.add_argument("--conv_checkpoint", default=None, help="run_models.py checkpoint ({'xformer', 'args'}) for --conv")
     ap.add_argument("--embed_dim", type=int, default=128, help="--conv without checkpoint: channels")
     ap.add_argument("--init_seed", type=int, default=0, help="torch seed of the untrained (seeded) decoder weights")
     a = ap.parse_args(argv)
+    if a.rnn_list_size is not None:
+        if not a.crisp:
+            ap.error("--rnn_list_size needs --crisp (it list-decodes with the CRISP GRU)")
+        if not 1 <= a.rnn_list_size <= 8:
+            ap.error("--rnn_list_size must be 1 .. 8")
+    return a
+
+
+def _main(argv=None):
+    a = _parse_args(argv)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1:
         import torch.distributed as dist
@@ -360,7 +397,7 @@ def _main(argv=None):
         if not code.ml_supported(map=True):
             raise SystemExit("--bitwise_map: bitwise MAP covers N in {8, 16, 32, 64} with K <= 16")
         bmap = MAPMonteCarlo(code, snrs, a.test_size, a.batch_size, a.seed).run()
-    crisp = None
+    crisp = crispl = None
     if a.crisp:
         if a.crisp_checkpoint:
             from .datasets import rnn_from_checkpoint
@@ -379,6 +416,8 @@ def _main(argv=None):
         else:
             net, dec = seeded_crisp(code, a.rnn_feature_size, a.rnn_depth, a.init_seed)
         crisp = GRUMonteCarlo(code, net, dec, snrs, a.test_size, a.batch_size, a.seed).run()
+        if a.rnn_list_size:
+            crispl = GRUListMonteCarlo(code, net, dec, a.rnn_list_size, snrs, a.test_size, a.batch_size, a.seed).run()
     conv = None
     if a.conv:
         if a.conv_checkpoint:
@@ -415,6 +454,10 @@ def _main(argv=None):
         if crisp is not None:
             print("BLERs of RNN: {0}".format(crisp.bler))
             rec["crisp_gru"] = crisp.as_dict()
+        if crispl is not None:
+            print("BERs of RNN List decoding: {0}".format(crispl.ber))
+            print("BLERs of RNN List decoding: {0}".format(crispl.bler))
+            rec["crisp_gru_list"] = dict(crispl.as_dict(), list_size=a.rnn_list_size)
         if conv is not None:
             print("BLERs of Xformer: {0}".format(conv.bler))
             rec["conv"] = conv.as_dict()

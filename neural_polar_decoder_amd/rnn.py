@@ -342,6 +342,77 @@ class RNN_decoder:
                    "npd_gru_decode_count_sweep")
         return counters
 
+    # ------------------------------------------------------------------ list decoding (rnn_all.py:563-664)
+    MAX_LIST = 8
+
+    def _list_reason(self, net, L):
+        """Why list_decode refuses this configuration (None: it runs) -- npd_gru_list_decode's limits, checked before
+        any handle is built."""
+        if self.decoding_type != "y_input":
+            return (f"list_decode covers decoding_type 'y_input', got {self.decoding_type!r} (the reference's y_h0 "
+                    "branch reads `out` before any step has run, rnn_all.py:592-597)")
+        if self.reverse_order:
+            return "list_decode ignores reverse_order in the reference (rnn_all.py:614); decode in natural order"
+        if self.precision != "fp32":
+            return f"list_decode runs fp32 (path metrics are compared against each other), got precision {self.precision!r}"
+        if getattr(net, "bidirectional", False):
+            return "list_decode covers unidirectional nets (the reference's hidden list is (layers, B, F), rnn_all.py:608)"
+        if getattr(net, "rnn_type", None) != "GRU":
+            return "list_decode covers GRU cells (the reference's hidden list is a bare tensor, rnn_all.py:608-610), not LSTM"
+        if isinstance(getattr(net, "layernorm", None), nn.LayerNorm):
+            return "list_decode does not cover the LayerNorm head (--use_layernorm)"
+        if getattr(net, "out_linear_depth", 1) != 1:
+            return "list_decode does not cover out_linear_depth > 1 heads"
+        if net.feature_size not in (32, 64):
+            return f"list_decode runs on the LDS-resident fp32 kernel: feature_size 32 or 64, got {net.feature_size}"
+        if not isinstance(L, (int, np.integer)) or not 1 <= int(L) <= self.MAX_LIST:
+            return f"list size L must be an integer in 1 .. {self.MAX_LIST}, got {L!r}"
+        if not (hasattr(net, "fused_supported") and net.fused_supported("y_input", "fp32", self.N)):
+            return "network configuration not supported by the fused GRU decoder"
+        return None
+
+    def list_supported(self, net, L) -> bool:
+        """True when list_decode(net, y, code, L) runs on the fused kernel (no handle is built)."""
+        return self._list_reason(net, L) is None
+
+    def list_decode(self, net, y, code, L=1, return_candidates=False):
+        """rnn_all.RNN_decoder.list_decode (rnn_all.py:580-664) in one fused launch (npd_gru_list_decode): the (B, K)
+        +-1 messages of the list survivor nearest to y.  `code` is this package's PolarCode or PAC (its information set
+        and encoder drive the final selection).  return_candidates: also (cand_msg (B, L, K), cand_metric (B, L),
+        sel (B) int32) -- the final list in the reference's order; unused slots (2^K < L) hold metric +inf, message 0."""
+        why = self._list_reason(net, L)
+        if why is not None:
+            raise _lib.NpdError(why)
+        L = int(L)
+        if net.input_size != self.N + 1 + int(self.onehot):
+            raise ValueError("net.input_size must be N + 1 + onehot")
+        ch = code._code_for(code.B) if hasattr(code, "pac_encode") else code.code
+        info = np.sort(np.asarray(self.info_inds, np.int64).reshape(-1))
+        if ch.N != self.N or not np.array_equal(info, ch.info):
+            raise _lib.NpdError("list_decode: the decoder's info_inds are not the code's information positions")
+        y_in = y
+        y = _lib.f32c(_lib.stage(y, "y"))
+        if y.dim() != 2 or y.shape[1] != self.N:
+            raise ValueError(f"y must be (batch, {self.N}), got {tuple(y.shape)}")
+        if y.data_ptr() % 16:
+            y = y.clone()
+        fy = _ymlp_forward(net, y) if net.y_depth > 0 else None  # --use_ynn: Fy feeds the GRU, y the final selection
+        B, K = y.shape[0], ch.K
+        h = self._handle(net, y.device)
+        hat = torch.empty(B, K, dtype=torch.float32, device=y.device)
+        cm = cmet = sel = None
+        if return_candidates:
+            cm = torch.empty(B, L, K, dtype=torch.float32, device=y.device)
+            cmet = torch.empty(B, L, dtype=torch.float32, device=y.device)
+            sel = torch.empty(B, dtype=torch.int32, device=y.device)
+        _lib.check(_lib.load().npd_gru_list_decode(h.h, ch.h, _lib.ptr(y), _lib.ptr(fy), L, _lib.ptr(hat), _lib.ptr(sel),
+                                                   _lib.ptr(cm), _lib.ptr(cmet), B, _lib.stream_of(y.device)),
+                   "npd_gru_list_decode")
+        hat = _lib.home(hat, y_in)
+        if return_candidates:
+            return hat, (_lib.home(cm, y_in), _lib.home(cmet, y_in), _lib.home(sel, y_in))
+        return hat
+
     def _h0(self, net, y):
         """(B, F * layers) initial states: get_h0's MLP (y first when the net was built with skip, rnn_all.py:369-370),
         kept alive past the stream-ordered decode by the caller."""
