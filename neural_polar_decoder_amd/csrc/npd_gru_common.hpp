@@ -1,5 +1,6 @@
-// npd_gru_common.hpp -- what the GRU kernels of npd_gru.hip and npd_gru_list.hip share: the handle, the MFMA tile
-// geometry (Geo, hid_of), the LDS weight image layout, gemm_chain and the gate math.
+// npd_gru_common.hpp -- what the RNN decoder kernels share (npd_gru.hip, npd_gru_lstm.hip, npd_gru_split.hip,
+// npd_gru_split16.hip, npd_gru_wide.hip, npd_gru_list.hip): the handle, the MFMA tile geometry (Geo, LGeo, hid_of), the
+// LDS weight image layout, gemm_chain and the gate math.  Host-only declarations are in npd_gru_host.hpp.
 #pragma once
 
 #include "npd_common.hpp"
@@ -58,6 +59,23 @@ struct Geo {
     static constexpr int OFF_CV = OFF_WL + 2 * HT * 16;
     static constexpr int TOTAL = OFF_CV + (2 * HT + TT) * 32;
 };
+
+// LSTM cells (lstm_decode_kernel, lstm_wide_kernel): Geo with 4F gate rows i, f, g, o
+template <int F, int L>
+struct LGeo {
+    static constexpr int TT = 4 * F / 32;
+    static constexpr int HT = F / 32;
+    static constexpr int KS = F / 2;
+    static constexpr int KG = KS / 4;
+    static constexpr int NG = (L == 2) ? 3 : 1;
+    static constexpr int G_SIZE = TT * KG * 64 * 4;
+    static constexpr int OFF_X = NG * G_SIZE;           // layer-0 [1, x_i] k-step A operands [TT][64]
+    static constexpr int OFF_WL = OFF_X + TT * 64;       // linear weights [half][HT][16]
+    static constexpr int OFF_CV = OFF_WL + 2 * HT * 16;  // bias tiles in accumulator order: [layer][TT][half][16]
+    static constexpr int TOTAL = OFF_CV + L * TT * 32;
+};
+
+__device__ __forceinline__ float sig2(float a) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(a)); }
 
 // hidden unit fed by lane half `kk` at k-step s (accumulator row map of the 32x32 MFMA tile)
 __host__ __device__ inline int hid_of(int s, int kk) {

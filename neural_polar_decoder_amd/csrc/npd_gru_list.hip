@@ -19,7 +19,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "npd_gru_common.hpp"
+#include "npd_gru_host.hpp"
 #include "npd_nth.hpp"
 
 namespace npd {
@@ -428,8 +428,6 @@ extern "C" int npd_gru_list_decode(const npd_gru* g, const npd_code* code, const
     for (int i = 0; i < g->N; ++i)
         if (!((code->p.frozen[i >> 5] >> (i & 31)) & 1u)) a.info[i >> 5] |= 1u << (i & 31);
     hipStream_t s = (hipStream_t)stream;
-    if (g->F == 64 && g->layers == 2) return gru::launch_list<64, 2>(a, s);
-    if (g->F == 64) return gru::launch_list<64, 1>(a, s);
-    if (g->layers == 2) return gru::launch_list<32, 2>(a, s);
-    return gru::launch_list<32, 1>(a, s);
+    return gru::dispatch(gru::NarrowShapes{}, [&](auto f, auto l) { return gru::launch_list<f.value, l.value>(a, s); },
+                         g->F, g->layers);
 }

@@ -1,0 +1,473 @@
+// npd_gru_split16.hip -- gru16p_kernel, the headline kernel: the split 16-bit MFMA paths on 16-codeword waves.
+// =============================================================================== split paths, 16-codeword waves
+// F = 64, 2 layers (the metric's CRISP GRU), split precisions, N a multiple of 32.  The 32-codeword split kernels
+// above need ~500 registers (P, both states, the gate accumulators): one wave per SIMD, and a step is one serial
+// chain (layer-0 GEMM -> update -> split -> layer-1 GEMM -> update -> output -> decision) that leaves the MFMA pipe
+// idle while the wave does its VALU work.  Here a wave owns 16 codewords on v_mfma_f32_16x16x32_{f16,bf16} (the same
+// FLOP per cycle as 32x32x16), so every register array halves and TWO waves share each SIMD, hiding each other's
+// LDS and dependency latencies.  (They do not hide each other's VALU work behind MFMAs: measured, an fp16 MFMA wave
+// and an FMA wave on one SIMD take the sum of their times, profiles/round3/coissue.txt; PMC: MFMA busy + VALU
+// active ~ all SIMD cycles.  Hence the VALU trims below: no fp32 k-step MFMAs, folded gate constants, permlane
+// reductions, immediate-offset LDS reads.)
+// 16x16x32 maps: lane l = 16 g + c holds D[row 4g + i][codeword c] (i = 0..3), A[row c][k 8g + j], B[k 8g + j][col c].
+// Hidden units form 16-row tiles ht = 0..3; K block kb (32 units) is tiles 2kb, 2kb + 1, with MFMA k index 8g + j
+// <-> hidden unit 16 (2kb + (j >> 2)) + 4g + (j & 3): an updated state tile converts register for register into the
+// next GEMM's B fragment (no lane movement); the host permutes the weight images to match.
+// Constants: layer 0's biases and one-hot column 0 enter P once per codeword, the x_i column is one FMA per
+// accumulator element, layer 1's biases initialise its accumulators from LDS: no fp32 k-step MFMAs.
+// The arithmetic per element (split products, fp32 accumulation, gate nonlinearities) is the 32-codeword kernels'.
+#include "npd_gru_split.hpp"
+
+namespace npd {
+namespace gru {
+
+struct Geo16 {
+    static constexpr int RT = 12, KB = 2, NG = 3;    // 16-row gate tiles, 32-unit K blocks, weight matrices
+    static constexpr int IMG4 = NG * RT * KB * 64;   // 16-B fragments per split image
+    // fragment (matrix g, row tile t, K block kb, part p = hi / lo) of lane l at f4 index (((g RT + t) KB + kb) 2 + p) 64 + l:
+    // a matrix spans 48 KB, so every read of a GEMM is an immediate offset (< 64 KB) from one per-lane base
+    static constexpr int G_BYTES = RT * KB * 2 * 1024;
+    static constexpr int OFF_C = 2 * IMG4 * 4;       // floats: constants after the weight fragments
+    static constexpr int C0L0 = OFF_C, C1L0 = OFF_C + 192, BHN0 = OFF_C + 384, C0L1 = OFF_C + 448,
+                         BHN1 = OFF_C + 640, WLIN = OFF_C + 704, TOTAL = OFF_C + 768;
+};
+
+__device__ __forceinline__ f4 mfma16s(const hf8& a, const hf8& b, const f4& c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
+}
+__device__ __forceinline__ f4 mfma16s(const bf8& a, const bf8& b, const f4& c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+}
+
+// B fragments of a state: fragment kb, element j = tile 2kb + (j >> 2), register j & 3 (hi and, split, lo)
+template <int SPLIT>
+__device__ __forceinline__ void split16s(const f4 (&h)[4], typename SplitT<SPLIT>::V (&hi)[2],
+                                         typename SplitT<SPLIT>::V (&lo)[2]) {
+    using S = SplitT<SPLIT>;
+#pragma unroll
+    for (int kb = 0; kb < 2; ++kb)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float v = h[2 * kb + (j >> 2)][j & 3] * S::kIn;
+            const typename S::E b = (typename S::E)v;
+            hi[kb][j] = b;
+            if (S::kLo) lo[kb][j] = (typename S::E)(v - (float)b);
+        }
+}
+
+// LDS fragment of the 16-codeword image: wb = this lane's byte base of the matrix (laundered once per kernel)
+__device__ __forceinline__ f4 frag16(const f4* __restrict__ smem4, uint32_t wb, int t, int kb, int part) {
+    return *reinterpret_cast<const f4*>(reinterpret_cast<const char*>(smem4) + wb +
+                                        ((t * Geo16::KB + kb) * 2 + part) * 1024);
+}
+
+// (p_row0 + p_row1) + (p_row2 + p_row3) over the four 16-lane rows, the same in every lane (the order of
+// __shfl_xor 16 then 32) on v_permlane16_swap / v_permlane32_swap: VALU, no LDS round trip
+__device__ __forceinline__ float sum_rows16(float p) {
+    const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(p), __float_as_uint(p), false, false);
+    const float s = __uint_as_float(r[0]) + __uint_as_float(r[1]);
+    const auto r2 = __builtin_amdgcn_permlane32_swap(__float_as_uint(s), __float_as_uint(s), false, false);
+    return __uint_as_float(r2[0]) + __uint_as_float(r2[1]);
+}
+
+__device__ __forceinline__ f4 fma4(float x, const f4& c, const f4& p) {
+    return f4{fmaf(x, c[0], p[0]), fmaf(x, c[1], p[1]), fmaf(x, c[2], p[2]), fmaf(x, c[3], p[3])};
+}
+
+#define NPD_GRU16_WPB 8
+// ---- the step is software-pipelined (measured 14.86 -> 14.42 ms per 2^20 words against the plain tile-by-tile
+// order, profiles/round3/gru_split_ab.txt; the plain order was removed in round 4).  A wave's own VALU instructions issue in the gaps of its 16-bit
+// MFMAs (8 of the 16 cycles of a 16x16x32 are busy for vector issue, MI355X_MICROARCH.md), while another wave's
+// do not (profiles/round3/coissue.txt: an fp16 MFMA wave and an FMA wave on one SIMD take the sum of their times).
+// So each hidden tile's GEMM carries the update of the PREVIOUS tile (cut into 12 chunks of ~5 instructions:
+// element i, stage 0 exp2s / 1 rcps + n-gate input + exp2 / 2 rcp + blend), spread over its MFMA triples between
+// sched_barrier fences; the h1 update of tile 3, the output, the decision and the h1 split ride on the NEXT step's
+// layer-0 tile-0 GEMM (which needs only h0', not x_i: the x_i column and P are added after it).
+template <int SPLIT>
+struct Upd4 {
+    f4 er, ez, en, z;
+    template <int C>
+    __device__ __forceinline__ void step(f4& h, const f4& ar, const f4& az, const f4& ain, const f4& ahn) {
+        constexpr float c1 = SplitT<SPLIT>::kC1, c2 = SplitT<SPLIT>::kC2;
+        constexpr int i = C / 3, st = C % 3;
+        if constexpr (st == 0) {
+            er[i] = __builtin_amdgcn_exp2f(c1 * ar[i]);
+            ez[i] = __builtin_amdgcn_exp2f(c1 * az[i]);
+        } else if constexpr (st == 1) {
+            const float r = __builtin_amdgcn_rcpf(1.0f + er[i]);
+            z[i] = __builtin_amdgcn_rcpf(1.0f + ez[i]);
+            en[i] = __builtin_amdgcn_exp2f(c2 * (ain[i] + ahn[i] * r));
+        } else {
+            const float nn = fmaf(2.0f, __builtin_amdgcn_rcpf(1.0f + en[i]), -1.0f);
+            h[i] = (h[i] - nn) * z[i] + nn;
+        }
+    }
+};
+
+template <int SPLIT>
+__device__ __forceinline__ void split_kb(const f4 (&h)[4], int kb, typename SplitT<SPLIT>::V (&hi)[2],
+                                         typename SplitT<SPLIT>::V (&lo)[2]) {
+    using S = SplitT<SPLIT>;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const float v = h[2 * kb + (j >> 2)][j & 3] * S::kIn;
+        const typename S::E b = (typename S::E)v;
+        hi[kb][j] = b;
+        if (S::kLo) lo[kb][j] = (typename S::E)(v - (float)b);
+    }
+}
+
+// A fragments (hi, lo) of one K block of a GEMM's NU row tiles
+template <int SPLIT, int NU>
+struct Frag16 {
+    typename SplitT<SPLIT>::V h[NU], l[NU];
+};
+template <int SPLIT, int NU>
+__device__ __forceinline__ void load_kb16(const f4* __restrict__ smem4, uint32_t wb, const int (&t)[NU], int kb,
+                                          Frag16<SPLIT, NU>& f) {
+    using V = typename SplitT<SPLIT>::V;
+#pragma unroll
+    for (int u = 0; u < NU; ++u) {
+        f.h[u] = __builtin_bit_cast(V, frag16(smem4, wb, t[u], kb, 0));
+        if (SplitT<SPLIT>::kLo) f.l[u] = __builtin_bit_cast(V, frag16(smem4, wb, t[u], kb, 1));
+    }
+}
+
+// acc[u] += W_g[row tile t[u]] . state (both K blocks); work(IC<c>) for chunks C0 .. C0 + NCH - 1 spread evenly
+// over the 2 NU MFMA triples, one sched_barrier-fenced region per triple.  The K block 0 fragments arrive in `cur`,
+// loaded by the previous GEMM, and this GEMM loads the next one's (matrix base wbn, tiles tn) into it once its own
+// K block 0 triples have issued, so no GEMM starts on an LDS round trip (measured 13.08-13.13 against 13.21-13.25 ms
+// per 2^20 words with each GEMM loading its own fragments, profiles/round5/gru16_ab.txt).
+template <int SPLIT, int NU, int C0, int NCH, typename Work>
+__device__ __forceinline__ void gemm16i(const f4* __restrict__ smem4, uint32_t wb, const int (&t)[NU],
+                                        f4 (&acc)[NU], const typename SplitT<SPLIT>::V (&bh)[2],
+                                        const typename SplitT<SPLIT>::V (&bl)[2], Frag16<SPLIT, NU>& cur,
+                                        uint32_t wbn, const int (&tn)[NU], Work&& work) {
+    constexpr int NT = 2 * NU;
+    Frag16<SPLIT, NU> f[2];  // f[1]: this GEMM's K block 1 (K block 0 is `cur`)
+    load_kb16<SPLIT, NU>(smem4, wb, t, 1, f[1]);
+    asm volatile("" ::: "memory");  // keeps the (loop-invariant) LDS fragment reads in the step loop
+    static_for<0, NT>([&](auto trc) {
+        constexpr int tr = decltype(trc)::value;
+        constexpr int kb = tr / NU, u = tr % NU;
+        const Frag16<SPLIT, NU>& F = kb == 0 ? cur : f[kb];
+        acc[u] = mfma16s(F.h[u], bh[kb], acc[u]);
+        if (SplitT<SPLIT>::kLo) {
+            acc[u] = mfma16s(F.h[u], bl[kb], acc[u]);
+            acc[u] = mfma16s(F.l[u], bh[kb], acc[u]);
+        }
+        if constexpr (tr == NU - 1) {
+            asm volatile("" ::: "memory");
+            load_kb16<SPLIT, NU>(smem4, wbn, tn, 0, cur);
+        }
+        static_for<C0 + NCH * tr / NT, C0 + NCH * (tr + 1) / NT>([&](auto cc) { work(cc); });
+        __builtin_amdgcn_sched_barrier(0);
+    });
+}
+
+template <int SPLIT>
+__global__ __launch_bounds__(64 * NPD_GRU16_WPB) void gru16p_kernel(const ArgsB a) {
+    using G = Geo16;
+    using S = SplitT<SPLIT>;
+    using V = typename S::V;
+    using E = typename S::E;
+    extern __shared__ __attribute__((aligned(16))) f4 smem4[];
+    {
+        const f4* src = reinterpret_cast<const f4*>(a.img);
+        for (int i = threadIdx.x; i < G::TOTAL / 4; i += blockDim.x) smem4[i] = src[i];
+        __syncthreads();
+    }
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int g4 = lane >> 4;
+    const int col = lane & 15;
+    const int N = a.N;
+    const int nkb = N / 32;
+    const int64_t tps = (a.B + 15) / 16;  // tiles per segment
+    const int64_t ntiles = tps * (a.nseg > 1 ? a.nseg : 1);
+    const bool count = a.counters != nullptr;
+    uint32_t be_w = 0, bl_w = 0;  // this wave's bit / block errors of the current segment (wave-uniform)
+    // per-lane LDS byte bases, laundered so that every fragment / constant read is base + immediate offset
+    uint32_t wbs[3];
+#pragma unroll
+    for (int g = 0; g < 3; ++g) {
+        uint32_t v = g * G::G_BYTES + lane * 16;
+        asm volatile("" : "+v"(v));
+        wbs[g] = v;
+    }
+    uint32_t cb = (G::OFF_C + 4 * g4) * 4;
+    asm volatile("" : "+v"(cb));
+    auto c4 = [&](int off, int t) -> f4 {
+        return *reinterpret_cast<const f4*>(reinterpret_cast<const char*>(smem4) + cb + (off - G::OFF_C + 16 * t) * 4);
+    };
+    const f4 zero = {0.f, 0.f, 0.f, 0.f};
+    constexpr int T0[3] = {0, 4, 8};
+    auto nowork = [](auto) {};
+
+    for (int64_t tile = (int64_t)blockIdx.x * NPD_GRU16_WPB + wave; tile < ntiles;
+         tile += (int64_t)gridDim.x * NPD_GRU16_WPB) {
+        const int64_t seg = tile / tps;
+        const int64_t cw = (tile - seg * tps) * 16 + col;  // codeword within the segment
+        const bool valid = cw < a.B;
+        const int64_t cwc = valid ? cw : a.B - 1;
+        const int64_t rowoff = (seg * a.B + cw) * N;       // this codeword's row of y / decoded / logits
+        // count mode: the codeword's messages as 2-bit codes of rint(msg) (-1: 0, +1: 1, 0: 2, else 3; the decision
+        // d is in {-1, 0, +1}), slot sl held by row sl & 3 at bits 2 (q & 15) of word q >> 4, q = sl >> 2: 4 registers
+        // cover K <= 256, loaded once per tile, so no step waits on a message load
+        uint32_t mc[4] = {0u, 0u, 0u, 0u};
+        if (count) {
+            const float* mr = a.msg + cwc * a.K;
+#pragma unroll
+            for (int w = 0; w < 4; ++w)
+                for (int j = 0; j < 16; ++j) {
+                    const int sl = 4 * (16 * w + j) + g4;
+                    if (sl >= a.K) break;
+                    const float v = rintf(mr[sl]);
+                    const uint32_t code = v == -1.0f ? 0u : v == 1.0f ? 1u : v == 0.0f ? 2u : 3u;
+                    mc[w] |= code << (2 * j);
+                }
+        }
+        uint32_t nerr = 0;  // this row's share of the codeword's bit errors
+        f4 P[G::RT];
+#pragma unroll
+        for (int t = 0; t < G::RT; ++t) P[t] = c4(G::C0L0, t);
+        if (a.y) {
+            const float* yr = a.y + (seg * a.B + cwc) * N;
+            for (int kb = 0; kb < nkb; ++kb) {
+                const f4 y0 = *reinterpret_cast<const f4*>(yr + 32 * kb + 8 * g4);
+                const f4 y1 = *reinterpret_cast<const f4*>(yr + 32 * kb + 8 * g4 + 4);
+                V yh, yl;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const float v = (j < 4 ? y0[j] : y1[j - 4]) * S::kIn;
+                    yh[j] = (E)v;
+                    if (S::kLo) yl[j] = (E)(v - (float)yh[j]);
+                }
+#pragma unroll
+                for (int t = 0; t < G::RT; ++t) {
+                    const V wh = __builtin_bit_cast(V, a.wy[(t * nkb + kb) * 64 + lane]);
+                    P[t] = mfma16s(wh, yh, P[t]);
+                    if (S::kLo) {
+                        const V wl = __builtin_bit_cast(V, a.wy[a.wy_lo + (t * nkb + kb) * 64 + lane]);
+                        P[t] = mfma16s(wh, yl, P[t]);
+                        P[t] = mfma16s(wl, yh, P[t]);
+                    }
+                }
+            }
+        }
+        f4 h0[4], h1[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            h0[t] = zero;
+            h1[t] = zero;
+        }
+        if (a.h0) {  // register e of tile t = hidden unit 16 t + 4 g4 + e of codeword col (F = 64, 2 layers)
+            const float* hr = a.h0 + (seg * a.B + cwc) * 128;
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int f = 16 * t + 4 * g4 + e;
+                    h0[t][e] = hr[2 * f];
+                    h1[t][e] = hr[2 * f + 1];
+                }
+        }
+        V fh[2], fl[2], gh[2], gl[2];
+        split16s<SPLIT>(h0, fh, fl);
+        split16s<SPLIT>(h1, gh, gl);
+        float xb = 1.0f;
+        // layer 0, hidden tile 0 of step 0: W_hh0 h0 part (the x_i column and P are added at the top of the step)
+        f4 a0[3] = {zero, zero, c4(G::BHN0, 0)};
+        constexpr int T1[3] = {1, 5, 9};
+        Frag16<SPLIT, 3> cur;
+        load_kb16<SPLIT, 3>(smem4, wbs[0], T0, 0, cur);
+        gemm16i<SPLIT, 3, 0, 0>(smem4, wbs[0], T0, a0, fh, fl, cur, wbs[0], T1, nowork);
+        for (int ii = 0; ii < N; ++ii) {
+            const int jj = a.rev ? N - 1 - ii : ii;
+            Upd4<SPLIT> u;
+            // count mode: this step's message slot (255: not compared), from the kernel arguments by a scalar load
+            const int sl = count ? (int)((a.slotw[jj >> 2] >> (8 * (jj & 3))) & 255u) : 255;
+            // ================= layer 0
+            f4 ap[3] = {a0[0] + fma4(xb, c4(G::C1L0, 0), P[0]), a0[1] + fma4(xb, c4(G::C1L0, 4), P[4]), a0[2]};
+            f4 ainp = fma4(xb, c4(G::C1L0, 8), P[8]);
+            static_for<1, 4>([&](auto htc) {
+                constexpr int ht = decltype(htc)::value;
+                const int T[3] = {ht, 4 + ht, 8 + ht};
+                f4 acc[3] = {fma4(xb, c4(G::C1L0, ht), P[ht]), fma4(xb, c4(G::C1L0, 4 + ht), P[4 + ht]),
+                             c4(G::BHN0, ht)};
+                constexpr int TN[3] = {ht < 3 ? ht + 1 : 0, ht < 3 ? 5 + ht : 4, ht < 3 ? 9 + ht : 8};
+                gemm16i<SPLIT, 3, 0, 12>(smem4, wbs[0], T, acc, fh, fl, cur, wbs[ht < 3 ? 0 : 2], TN, [&](auto cc) {
+                    u.template step<decltype(cc)::value>(h0[ht - 1], ap[0], ap[1], ainp, ap[2]);
+                });
+                ainp = fma4(xb, c4(G::C1L0, 8 + ht), P[8 + ht]);
+#pragma unroll
+                for (int k = 0; k < 3; ++k) ap[k] = acc[k];
+            });
+            // ================= layer 1, hidden tile 0: W_hh1 h1 beside h0 tile 3's update and the h0' split
+            f4 b[3] = {c4(G::C0L1, 0), c4(G::C0L1, 4), c4(G::BHN1, 0)};
+            gemm16i<SPLIT, 3, 0, 14>(smem4, wbs[2], T0, b, gh, gl, cur, wbs[1], T0, [&](auto cc) {
+                constexpr int c = decltype(cc)::value;
+                if constexpr (c < 12) u.template step<c>(h0[3], ap[0], ap[1], ainp, ap[2]);
+                else split_kb<SPLIT>(h0, c - 12, fh, fl);
+            });
+            f4 bi[3] = {b[0], b[1], c4(G::C0L1, 8)};
+            gemm16i<SPLIT, 3, 0, 0>(smem4, wbs[1], T0, bi, fh, fl, cur, wbs[2], T1, nowork);
+            f4 q[4] = {bi[0], bi[1], bi[2], b[2]};  // r, z, in, hn of the previous layer-1 tile
+            float part = 0.0f;
+            static_for<1, 4>([&](auto htc) {
+                constexpr int ht = decltype(htc)::value;
+                const int T[3] = {ht, 4 + ht, 8 + ht};
+                f4 bb[3] = {c4(G::C0L1, ht), c4(G::C0L1, 4 + ht), c4(G::BHN1, ht)};
+                auto work = [&](auto cc) {
+                    constexpr int c = decltype(cc)::value;
+                    if constexpr (c < 12) {
+                        u.template step<c>(h1[ht - 1], q[0], q[1], q[2], q[3]);
+                    } else {
+                        const f4 wl = c4(G::WLIN, ht - 1);
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) part = fmaf(wl[i], h1[ht - 1][i], part);
+                    }
+                };
+                gemm16i<SPLIT, 3, 0, 7>(smem4, wbs[2], T, bb, gh, gl, cur, wbs[1], T, work);
+                f4 bbi[3] = {bb[0], bb[1], c4(G::C0L1, 8 + ht)};
+                constexpr int TN[3] = {ht < 3 ? ht + 1 : 0, ht < 3 ? 5 + ht : 4, ht < 3 ? 9 + ht : 8};
+                gemm16i<SPLIT, 3, 7, 6>(smem4, wbs[1], T, bbi, fh, fl, cur, wbs[ht < 3 ? 2 : 0], TN, work);
+                q[0] = bbi[0];
+                q[1] = bbi[1];
+                q[2] = bbi[2];
+                q[3] = bb[2];
+            });
+            // ================= tail: next step's layer-0 tile-0 GEMM beside h1 tile 3's update, the output, the
+            // decision and the h1 split
+            a0[0] = zero;
+            a0[1] = zero;
+            a0[2] = c4(G::BHN0, 0);
+            gemm16i<SPLIT, 3, 0, 15>(smem4, wbs[0], T0, a0, fh, fl, cur, wbs[0], T1, [&](auto cc) {
+                constexpr int c = decltype(cc)::value;
+                if constexpr (c < 12) {
+                    u.template step<c>(h1[3], q[0], q[1], q[2], q[3]);
+                } else if constexpr (c == 12) {
+                    const f4 wl = c4(G::WLIN, 3);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) part = fmaf(wl[i], h1[3][i], part);
+                    const float out = sum_rows16(part) + a.b_lin;
+                    const bool info = (a.info[jj >> 5] >> (jj & 31)) & 1u;
+                    float d;
+                    if (info) d = out > 0.0f ? 1.0f : (out < 0.0f ? -1.0f : 0.0f);
+                    else d = a.gt ? a.gt[(seg * a.B + cwc) * N + jj] : 1.0f;
+                    if (g4 == 0 && valid) {
+                        if (a.decoded) a.decoded[rowoff + jj] = d;
+                        if (a.logits) a.logits[rowoff + ii] = out;
+                    }
+                    if (sl != 255) {  // count_errors_kernel's test, rint(msg) != rint(d), on the 2-bit codes
+                        const int q = sl >> 2, w = q >> 4;
+                        const uint32_t mw = w == 0 ? mc[0] : w == 1 ? mc[1] : w == 2 ? mc[2] : mc[3];
+                        const uint32_t dc = d > 0.0f ? 1u : (d < 0.0f ? 0u : 2u);
+                        nerr += (g4 == (sl & 3) && ((mw >> (2 * (q & 15))) & 3u) != dc) ? 1u : 0u;
+                    }
+                    const float sd = d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f);
+                    xb = a.onehot ? (sd > 0.0f ? 1.0f : 0.0f) : sd;
+                } else {
+                    split_kb<SPLIT>(h1, c - 13, gh, gl);
+                }
+            });
+        }
+        if (count) {
+            // the 16 codewords' errors: each row counted its slots; sum the four rows of every codeword
+            nerr += __shfl_xor(nerr, 16, 64);
+            nerr += __shfl_xor(nerr, 32, 64);
+            const bool mine = g4 == 0 && valid;
+            bl_w += (uint32_t)__builtin_popcountll(__ballot(mine && nerr != 0u));
+            uint32_t e = mine ? nerr : 0u;
+#pragma unroll
+            for (int o = 1; o < 16; o <<= 1) e += __shfl_xor(e, o, 64);
+            be_w += (uint32_t)__builtin_amdgcn_readfirstlane(e);
+            // flush when this wave's next tile is in another segment (or there is none): one atomic pair per
+            // wave and segment
+            const int64_t nt = tile + (int64_t)gridDim.x * NPD_GRU16_WPB;
+            if (nt >= ntiles || nt / tps != seg) {
+                if (lane == 0 && (be_w | bl_w)) {
+                    atomicAdd(a.counters + 2 * seg, (unsigned long long)be_w);
+                    atomicAdd(a.counters + 2 * seg + 1, (unsigned long long)bl_w);
+                }
+                be_w = bl_w = 0;
+            }
+        }
+    }
+}
+
+// image of gru16p_kernel: weight fragments (hi, lo) in the 16x16x32 A-operand order, constants x kc
+template <int SPLIT>
+static void build_image16(const float* W, int N, int onehot, std::vector<float>& img, std::vector<float>& wy,
+                          int64_t& wy_lo) {
+    using G = Geo16;
+    constexpr int F = 64, L = 2;
+    const int Din = N + (onehot ? 2 : 1);
+    const Weights u = unpack_weights(W, 3, F, L, Din);
+    const auto &wih = u.wih, &bih = u.bih, &bhh = u.bhh;
+    img.assign(G::TOTAL, 0.0f);
+    // SPLIT 5: every gate row pre-multiplied by its exp2 constant (r, z: -log2 e; n: -2 log2 e; one fp32 rounding)
+    auto fold = [&](int row) { return SPLIT == 5 ? (row < 2 * F ? -1.44269504088896340736f : -2.88539008177792681472f) : 1.0f; };
+    uint16_t* u16 = reinterpret_cast<uint16_t*>(img.data());
+    for (int g = 0; g < G::NG; ++g)
+        for (int t = 0; t < G::RT; ++t)
+            for (int kb = 0; kb < G::KB; ++kb)
+                for (int l = 0; l < 64; ++l)
+                    for (int j = 0; j < 8; ++j) {
+                        const int row = 16 * t + (l & 15);
+                        const int hid = 16 * (2 * kb + (j >> 2)) + 4 * (l >> 4) + (j & 3);
+                        uint16_t hi, lo;
+                        split16<SPLIT>(fold(row) * u.mats[g][(size_t)row * F + hid], hi, lo);
+                        const size_t e = (((((size_t)(g * G::RT + t) * G::KB + kb) * 2) * 64 + l) * 8 + j);
+                        u16[e] = hi;
+                        if (SPLIT >= 3) u16[e + 64 * 8] = lo;
+                    }
+    const float kc = SPLIT == 4 ? 65536.0f : 1.0f;
+    auto col = [&](int row, int k) { return wih[0][(size_t)row * Din + k]; };
+    for (int row = 0; row < 3 * F; ++row) {
+        const bool rz = row < 2 * F;
+        // x_i enters as c0 + x_i c1 (one-hot: columns N, N + 1 -> c0 = w_N, c1 = w_{N+1} - w_N; else c1 = w_N)
+        const float c0x = onehot ? col(row, N) : 0.0f;
+        const float c1x = onehot ? col(row, N + 1) - col(row, N) : col(row, N);
+        img[G::C0L0 + row] = fold(row) * (kc * (rz ? bih[0][row] + bhh[0][row] + c0x : bih[0][row] + c0x));
+        img[G::C1L0 + row] = fold(row) * (kc * c1x);
+        img[G::C0L1 + row] = fold(row) * (kc * (rz ? bih[1][row] + bhh[1][row] : bih[1][row]));
+    }
+    for (int j = 0; j < F; ++j) {
+        img[G::BHN0 + j] = fold(2 * F + j) * (kc * bhh[0][2 * F + j]);
+        img[G::BHN1 + j] = fold(2 * F + j) * (kc * bhh[1][2 * F + j]);
+        img[G::WLIN + j] = u.wlin[j];
+    }
+    wy_lo = fill_wy16<SPLIT>(wih[0], G::RT, 16, N, Din, fold, wy);
+}
+
+using Split16s = Combos<Combo<3>, Combo<5>, Combo<1>>;
+
+void build_image_split16(npd_gru& g, const float* W, HostImages& im) {
+    if (g.precision == 0 || g.F != 64 || g.layers != 2 || g.N % 32 != 0) return;
+    // fp16x3 here is the unscaled split with the gate constants folded into the weights (SPLIT 5); the
+    // 32-codeword kernels (other shapes) run the x 2^8-scaled split (SPLIT 4)
+    g.split16 = split_of(g.precision, true);
+    dispatch(Split16s{}, [&](auto sp) { build_image16<sp.value>(W, g.N, g.onehot, im.img16, im.wy16, g.wy16_lo); },
+             g.split16);
+}
+
+int launch_split16(const npd_gru* g, const ArgsB& b, hipStream_t s) {
+    const int64_t tiles = (b.B + 15) / 16 * (b.nseg > 1 ? b.nseg : 1);
+    const int grid = grid_for((tiles + NPD_GRU16_WPB - 1) / NPD_GRU16_WPB, 1, device_cu_count());
+    return dispatch(Split16s{}, [&](auto sp) {
+        return launch_lds<gru16p_kernel<sp.value>>("gru16p_kernel launch", grid, 64 * NPD_GRU16_WPB,
+                                                   (size_t)Geo16::TOTAL * 4, s, b);
+    }, g->split16);
+}
+
+int launch_split16_sweep(const npd_gru* g, const Args& a, int n_seg, const float* msg, int K,
+                         const uint8_t (&slot)[kMaxN], unsigned long long* counters, hipStream_t s) {
+    ArgsB b = make_args_b(g, a);
+    b.msg = msg; b.counters = counters; b.K = K; b.nseg = n_seg;
+    memcpy(b.slotw, slot, sizeof(slot));
+    return launch_split16(g, b, s);
+}
+
+}  // namespace gru
+}  // namespace npd

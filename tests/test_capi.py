@@ -65,6 +65,98 @@ def test_code_create_argument_errors():
     assert L.npd_code_destroy(out) == 0
 
 
+def _rnn_weight_count(gates, N, F, layers, onehot):
+    din = N + (2 if onehot else 1)
+    n = gates * F * din + gates * F * F + 2 * gates * F
+    if layers == 2:
+        n += 2 * gates * F * F + 2 * gates * F
+    return n + F + 1
+
+
+def test_rnn_create_argument_errors():
+    """Every refusal of npd_gru_create / npd_rnn_create / npd_rnn_create_ex: status -1, its message, a NULL out-handle.
+    All of them are decided before the first HIP call, so nothing is allocated and no GPU is needed."""
+    from neural_polar_decoder_amd import _lib
+    L = _lib.load()
+    # read only by the LayerNorm fold (n_weights floats, before npd_gru_create counts them): large enough for that case
+    buf = np.zeros(8192, dtype=np.float32)
+    w = buf.ctypes.data_as(ctypes.c_void_p)
+    ln = np.ones(64, dtype=np.float32)
+    lnp = ln.ctypes.data_as(ctypes.c_void_p)
+
+    def nw(N, F, layers, onehot=1, gates=3):
+        return _rnn_weight_count(gates, N, F, layers, onehot)
+
+    # (N, F, layers, onehot, n_weights, precision), message
+    gru_cases = [
+        ((12, 32, 1, 1, nw(12, 32, 1), 0), b"multiple of 8"),
+        ((16, 48, 1, 1, nw(16, 48, 1), 0), b"hidden size F must be"),
+        ((16, 128, 1, 1, nw(16, 128, 1), 3), b"cover F <= 64"),
+        ((256, 512, 2, 1, nw(256, 512, 2), 0), b"needs N <= 128"),
+        ((16, 32, 3, 1, nw(16, 32, 2), 0), b"1 or 2 GRU layers"),
+        ((16, 32, 1, 1, nw(16, 32, 1), 4), b"precision must be"),
+        ((8, 32, 1, 1, nw(8, 32, 1), 3), b"N % 16"),
+        ((16, 32, 1, 1, nw(16, 32, 1) + 1, 0), b"weight count does not match (N, F"),
+        ((16, 32, 1, 1, nw(16, 32, 1) - 1, 0), b"weight count does not match (N, F"),
+        ((16, 64, 2, 0, nw(16, 64, 2, 1), 0), b"weight count does not match (N, F"),
+    ]
+    for (N, F, layers, onehot, n, prec), msg in gru_cases:
+        out = ctypes.c_void_p(0xdead)
+        rc = L.npd_gru_create(N, F, layers, onehot, w, n, prec, ctypes.byref(out))
+        assert rc == -1 and msg in L.npd_last_error() and out.value is None, (N, F, layers, prec, rc, L.npd_last_error())
+    out = ctypes.c_void_p(0xdead)
+    assert L.npd_gru_create(16, 32, 1, 1, None, nw(16, 32, 1), 0, ctypes.byref(out)) == -1
+    assert b"weights is NULL" in L.npd_last_error() and out.value is None
+    assert L.npd_gru_create(16, 32, 1, 1, w, nw(16, 32, 1), 0, None) == -1
+    assert b"out is NULL" in L.npd_last_error()
+
+    # (cell, N, F, layers, onehot, n_weights, precision), message
+    rnn_cases = [
+        ((2, 16, 32, 1, 1, nw(16, 32, 1), 0), b"cell must be"),
+        ((1, 16, 32, 1, 1, nw(16, 32, 1, gates=4), 3), b"LSTM cells run fp32"),
+        ((1, 16, 32, 1, 1, nw(16, 32, 1, gates=4) + 1, 0), b"(LSTM"),
+        ((1, 16, 64, 2, 1, nw(16, 64, 2, gates=4) - 1, 0), b"(LSTM"),
+        ((1, 12, 32, 1, 1, nw(12, 32, 1, gates=4), 0), b"multiple of 8"),
+        ((1, 16, 48, 1, 1, nw(16, 48, 1, gates=4), 0), b"LSTM hidden size F must be"),
+        ((1, 256, 512, 2, 1, nw(256, 512, 2, gates=4), 0), b"needs N <= 128"),
+        ((1, 16, 32, 3, 1, nw(16, 32, 2, gates=4), 0), b"1 or 2 layers"),
+        ((0, 16, 48, 1, 1, nw(16, 48, 1), 0), b"npd_gru_create: hidden size F must be"),   # cell 0: the GRU ladder
+    ]
+    for (cell, N, F, layers, onehot, n, prec), msg in rnn_cases:
+        out = ctypes.c_void_p(0xdead)
+        rc = L.npd_rnn_create(cell, N, F, layers, onehot, w, n, prec, ctypes.byref(out))
+        assert rc == -1 and msg in L.npd_last_error() and out.value is None, (cell, N, F, layers, prec, rc,
+                                                                             L.npd_last_error())
+
+    def head_n(F, depth, H):
+        return H * F + H + (depth - 2) * (H * H + H) + H + 1
+
+    # (cell, N, F, layers, n_weights, precision, ln_weight, ln_bias, head_depth, head_hidden, head_weights, n_head), message
+    ex_cases = [
+        ((0, 16, 32, 1, nw(16, 32, 1), 0, None, None, 9, 20, w, head_n(32, 9, 20)), b"head_depth must be 1 .. 8"),
+        ((0, 16, 32, 1, nw(16, 32, 1), 0, None, None, 0, 20, w, 0), b"head_depth must be 1 .. 8"),
+        ((0, 16, 32, 1, nw(16, 32, 1), 0, lnp, lnp, 2, 20, w, head_n(32, 2, 20)), b"not fused"),
+        ((0, 16, 128, 1, nw(16, 128, 1), 0, None, None, 2, 20, w, head_n(128, 2, 20)),
+         b"out_linear_depth > 1 head runs on the fp32 GRU kernel"),
+        ((0, 16, 32, 1, nw(16, 32, 1), 0, None, None, 2, 129, w, head_n(32, 2, 129)),
+         b"out_linear_depth > 1 head runs on the fp32 GRU kernel"),
+        ((0, 16, 32, 1, nw(16, 32, 1), 0, None, None, 2, 20, None, head_n(32, 2, 20)), b"null pointer"),
+        ((0, 16, 32, 1, nw(16, 32, 1) + 1, 0, None, None, 2, 20, w, head_n(32, 2, 20)),
+         b"weight count does not match (N, F"),
+        ((0, 16, 32, 1, nw(16, 32, 1), 3, lnp, lnp, 1, 0, None, 0), b"LayerNorm head runs on the fp32 GRU kernel"),
+        ((1, 16, 32, 1, nw(16, 32, 1, gates=4), 0, lnp, lnp, 1, 0, None, 0),
+         b"LayerNorm head runs on the fp32 GRU kernel"),
+        ((0, 16, 32, 1, nw(16, 32, 1), 0, lnp, None, 1, 0, None, 0), b"null pointer"),
+        ((0, 16, 32, 1, nw(16, 32, 1) + 1, 0, lnp, lnp, 1, 0, None, 0), b"weight count does not match (N, F"),
+        ((2, 16, 32, 1, nw(16, 32, 1), 0, None, None, 1, 0, None, 0), b"cell must be"),    # plain head: npd_rnn_create's
+    ]
+    for (cell, N, F, layers, n, prec, lw, lb, depth, H, hw, nh), msg in ex_cases:
+        out = ctypes.c_void_p(0xdead)
+        rc = L.npd_rnn_create_ex(cell, N, F, layers, 1, w, n, prec, lw, lb, 1e-5, depth, H, hw, nh, ctypes.byref(out))
+        assert rc == -1 and msg in L.npd_last_error() and out.value is None, (cell, F, prec, depth, H, rc,
+                                                                             L.npd_last_error())
+
+
 def test_null_pointer_errors_are_reported_not_fatal():
     from neural_polar_decoder_amd import _lib
     L = _lib.load()

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B builds of libnpd.so with ONE source file compiled under experiment macros (tools/bin/libnpd_<name>.so, loaded
-# through NPD_LIB).  Usage: bash tools/build_variants.sh npd_gru "name:-DNPD_GRU16_ORDER=1" ...
+# through NPD_LIB).  Usage: bash tools/build_variants.sh npd_gru_split16 "name:-DNPD_GRU16_ORDER=1" ...
 set -e
 cd "$(dirname "$0")/.."
 src=$1; shift
