@@ -333,10 +333,11 @@ int npd_gru_decode_count_sweep(const npd_gru* gru, int n_seg, const float* y, co
  * Outputs, each optional but at least one of msg_hat and cand_msg: msg_hat (B,K) the chosen survivor's message (+-1),
  * sel (B) int32 its index in list order, cand_msg (B, list_size, K) and cand_metric (B, list_size) the final list in
  * the reference's order; unused slots (2^K < list_size) carry metric +inf and message 0.
- * One launch, no allocation, no host synchronisation; B = 0 returns NPD_OK.  Runs on the fp32 LDS-resident kernel:
- * GRU handles with precision 0, F 32 or 64, 1 or 2 layers and the plain Linear(F, 1) head -- LSTM, split-precision,
- * F >= 128, LayerNorm-head and out_linear_depth > 1 handles return NPD_ENOTSUP (npd_gru_list_supported tells
- * beforehand: 1 / 0, < 0 on NULL).  list_size = 1 is npd_gru_decode's greedy decision, bit for bit.
+ * One launch, no allocation, no host synchronisation; B = 0 returns NPD_OK.  Runs on the fp32 kernels: GRU handles
+ * with precision 0, 1 or 2 layers and the plain Linear(F, 1) head, at F 32 or 64 (weights in LDS) and at F 256 or 512
+ * (weights streamed, as npd_gru_decode at those widths, with its N limit) -- LSTM, split-precision, F = 128,
+ * LayerNorm-head and out_linear_depth > 1 handles return NPD_ENOTSUP (npd_gru_list_supported tells beforehand:
+ * 1 / 0, < 0 on NULL).  list_size = 1 is npd_gru_decode's greedy decision, bit for bit, at every width.
  * Decisions follow the reference's arithmetic in fp32 (gate nonlinearities to ~1 ulp, as npd_gru_decode), so a
  * survivor set can differ where two metrics are closer than the logits' tolerance, and two candidates whose fp32
  * distances differ only by summation order (torch's vectorised sum vs the kernel's) may swap in the final selection.

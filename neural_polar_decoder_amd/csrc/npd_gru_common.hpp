@@ -1,5 +1,5 @@
 // npd_gru_common.hpp -- what the RNN decoder kernels share (npd_gru.hip, npd_gru_lstm.hip, npd_gru_split.hip,
-// npd_gru_split16.hip, npd_gru_wide.hip, npd_gru_list.hip): the handle, the MFMA tile geometry (Geo, LGeo, hid_of), the
+// npd_gru_split16.hip, npd_gru_wide.hip, npd_gru_list.hip, npd_gru_wide_list.hip): the handle, the MFMA tile geometry (Geo, LGeo, hid_of), the
 // LDS weight image layout, gemm_chain and the gate math.  Host-only declarations are in npd_gru_host.hpp.
 #pragma once
 

@@ -16,54 +16,16 @@
 // (rank counting; npd_nth.hpp's statement of torch.topk when a tie straddles the L-th place), compacts them in
 // ascending child index and gathers state, bits and metric from the parent column with ds_bpermute_b32 inside the
 // lane half; the gather is skipped when no lane of the wave moves.
+//
+// This file also owns the C entry points of both list kernels; hidden 256 / 512 handles go to gru_wide_list_kernel
+// (npd_gru_wide_list.hip: the same column map and procedure on the weight-streaming step).
 #include <stdlib.h>
 #include <string.h>
 
-#include "npd_gru_host.hpp"
-#include "npd_nth.hpp"
+#include "npd_gru_list.hpp"
 
 namespace npd {
 namespace gru {
-
-struct ListArgs {
-    const float* img;
-    const f4* wy;
-    const float* y;    // (B, N) received words: final selection
-    const float* fy;   // (B, N) GRU input
-    float* msg_hat;    // (B, K) or NULL
-    int32_t* sel;      // (B) or NULL
-    float* cand_msg;   // (B, L, K) or NULL
-    float* cand_metric;  // (B, L) or NULL
-    int64_t B;
-    int N, K, L, lp_log2;
-    int onehot, pac;
-    float b_lin;
-    uint32_t tapmask, smask;
-    uint32_t info[kMaxWords];
-};
-
-typedef float f8v __attribute__((ext_vector_type(8)));
-
-// metric x beats metric y in pruneLists: torch.topk(-metric) with NaN as the largest value (nth::comp on the negated metrics)
-__device__ __forceinline__ bool beats(float x, float y) { return (x != x && y == y) || (x < y); }
-
-// survivors when a tie straddles the L-th place (rare): the reference's exact rule on the list order
-// [keep_0 .. keep_{s-1}, flip_0 .. flip_{s-1}].  Vectors by value (VGPRs), the queue lives on this function's stack.
-__device__ __noinline__ uint32_t list_exact_mask(f8v km, f8v fm, int s, int L) {
-    float v[16];
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-        v[t] = 0.0f;
-        v[8 + t] = 0.0f;
-    }
-#pragma unroll
-    for (int t = 0; t < 8; ++t)
-        if (t < s) {
-            v[t] = -1.0f * km[t];
-            v[s + t] = -1.0f * fm[t];
-        }
-    return nth::prune_mask(v, 2 * s, L);
-}
 
 template <int F, int L>
 __global__ __launch_bounds__(64 * NPD_GRU_WPB) void gru_list_kernel(const ListArgs a) {
@@ -88,7 +50,6 @@ __global__ __launch_bounds__(64 * NPD_GRU_WPB) void gru_list_kernel(const ListAr
     const int cpt = 32 >> lpl;     // codewords per wave tile
     const uint32_t gmask = (1u << Lp) - 1u;
     const int64_t ntiles = (a.B + cpt - 1) / cpt;
-    const float kInf = __builtin_inff();
     const f16v zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     auto cvec = [&](int off) -> f16v {
         const f4* p = reinterpret_cast<const f4*>(smem + off + half * 16);
@@ -197,52 +158,8 @@ __global__ __launch_bounds__(64 * NPD_GRU_WPB) void gru_list_kernel(const ListAr
                 if (flip) met += ao;
                 ls *= 2;
             } else {
-                // children in list order: c < ls keeps slot c's bit and metric, c >= ls flips slot c - ls's
-                const float mk = met, mf = met + ao;
-                f8v km, fm;
-#pragma unroll
-                for (int t = 0; t < 8; ++t) {
-                    const int sl = base + (t < ls ? t : 0);
-                    km[t] = __shfl(mk, sl, 64);
-                    fm[t] = __shfl(mf, sl, 64);
-                }
-                // rank counting for this slot's two children: nb candidates beat it, ne are equivalent (itself too)
-                int nbk = 0, nek = 0, nbf = 0, nef = 0;
-#pragma unroll
-                for (int t = 0; t < 8; ++t) {
-                    if (t < ls) {
-                        const bool b1 = beats(km[t], mk), e1 = !b1 && !beats(mk, km[t]);
-                        const bool b2 = beats(fm[t], mk), e2 = !b2 && !beats(mk, fm[t]);
-                        const bool b3 = beats(km[t], mf), e3 = !b3 && !beats(mf, km[t]);
-                        const bool b4 = beats(fm[t], mf), e4 = !b4 && !beats(mf, fm[t]);
-                        nbk += (int)b1 + (int)b2;
-                        nek += (int)e1 + (int)e2;
-                        nbf += (int)b3 + (int)b4;
-                        nef += (int)e3 + (int)e4;
-                    }
-                }
-                const bool mine = slot < ls;
-                const bool sk = mine && nbk < a.L, sf = mine && nbf < a.L;
-                // a class of equivalent metrics straddles the L-th place: the top-L set is not unique
-                const bool amb = (sk && nbk + nek > a.L) || (sf && nbf + nef > a.L);
-                const uint64_t bk = __ballot(sk), bf = __ballot(sf), ba = __ballot(amb);
-                uint32_t mask = ((uint32_t)(bk >> base) & gmask) | (((uint32_t)(bf >> base) & gmask) << ls);
-                if (((uint32_t)(ba >> base) & gmask) != 0u) mask = list_exact_mask(km, fm, ls, a.L);
-                // slot j takes the j-th survivor in ascending child index
-                int child = -1, cnt = 0;
-#pragma unroll
-                for (int c = 0; c < 16; ++c) {
-                    const int bit = (int)((mask >> c) & 1u);
-                    if (bit && cnt == slot) child = c;
-                    cnt += bit;
-                }
-                const bool live = slot < a.L && child >= 0;
-                flip = live && child >= ls;
-                const int src = live ? base + (flip ? child - ls : child) : lane;
                 // metric and bit always come from the parent; state and bit words only when some lane of the wave moves
-                const float pk = __shfl(mk, src, 64), pf = __shfl(mf, src, 64);
-                met = flip ? pf : pk;
-                neg = (uint32_t)__shfl((int)neg, src, 64);
+                const int src = list_prune(met, neg, flip, ao, ls, a.L, lane, slot, base, gmask);
                 if (__ballot(src != lane) != 0ull) {
 #pragma unroll
                     for (int t = 0; t < HT; ++t)
@@ -264,93 +181,7 @@ __global__ __launch_bounds__(64 * NPD_GRU_WPB) void gru_list_kernel(const ListAr
         }
 
         // ================= epilogue: encode every path, distance to y, first minimum over the live slots
-        uint32_t cd[kMaxWords];
-#pragma unroll
-        for (int w = 0; w < kMaxWords; ++w) cd[w] = bw[w];
-        if (a.pac) {
-            // rate-1 convolution (encode_kernel, npd_gen.hip): u_i = v_i xor parity(state & taps), state <- v
-            uint32_t st = 0;
-#pragma unroll
-            for (int w = 0; w < kMaxWords; ++w)
-                if (32 * w < N) {
-                    const uint32_t vin = bw[w];
-                    uint32_t uo = 0u;
-                    for (int b = 0; b < 32; ++b) {
-                        const uint32_t vi = (vin >> b) & 1u;
-                        uo |= (vi ^ ((uint32_t)__builtin_popcount(st & a.tapmask) & 1u)) << b;
-                        st = ((st << 1) | vi) & a.smask;
-                    }
-                    const int rem = N - 32 * w;
-                    cd[w] = rem >= 32 ? uo : (uo & ((1u << rem) - 1u));
-                }
-        }
-        // Plotkin butterfly over GF(2): x_i ^= x_{i+h} where bit h of i is clear (words past N are zero)
-        {
-            constexpr uint32_t km[5] = {0x55555555u, 0x33333333u, 0x0F0F0F0Fu, 0x00FF00FFu, 0x0000FFFFu};
-#pragma unroll
-            for (int s = 0; s < 5; ++s)
-#pragma unroll
-                for (int w = 0; w < kMaxWords; ++w) cd[w] ^= (cd[w] >> (1 << s)) & km[s];
-#pragma unroll
-            for (int hw = 1; hw < kMaxWords; hw <<= 1)
-#pragma unroll
-                for (int w = 0; w < kMaxWords; ++w)
-                    if ((w & hw) == 0) cd[w] ^= cd[w + hw];
-        }
-        // fp32 distance: each lane half sums 16 positions of every word
-        float ds = 0.0f;
-        {
-            const float* yrow = a.y + cwc * N;
-#pragma unroll
-            for (int w = 0; w < kMaxWords; ++w)
-                if (32 * w < N) {
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const int i0 = 32 * w + 16 * half + 4 * q;
-                        if (i0 < N) {
-                            const f4 yv = *reinterpret_cast<const f4*>(yrow + i0);
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) {
-                                const float c = ((cd[w] >> (16 * half + 4 * q + e)) & 1u) ? -1.0f : 1.0f;
-                                const float d = c - yv[e];
-                                ds = fmaf(d, d, ds);
-                            }
-                        }
-                    }
-                }
-        }
-        const float dist = ds + __shfl_xor(ds, 32, 64);
-        float best = 0.0f;
-        int bsel = 0;
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            const float dt = __shfl(dist, base + (t < ls ? t : 0), 64);
-            if (t == 0 || (t < ls && dt < best)) {
-                best = t == 0 ? dt : (dt < best ? dt : best);
-                bsel = t;
-            }
-        }
-        if (half == 0 && valid && slot < a.L) {
-            const bool alive = slot < ls;
-            const bool chosen = slot == bsel;
-            if (a.cand_metric) a.cand_metric[cw * a.L + slot] = alive ? met : kInf;
-            if (a.sel && chosen) a.sel[cw] = bsel;
-            float* cm = a.cand_msg ? a.cand_msg + (cw * a.L + slot) * (int64_t)a.K : nullptr;
-            float* mh = (a.msg_hat && chosen) ? a.msg_hat + cw * (int64_t)a.K : nullptr;
-            int k = 0;
-#pragma unroll
-            for (int w = 0; w < kMaxWords; ++w)
-                if (32 * w < N) {
-                    const uint32_t iw = a.info[w], vw = bw[w];
-                    for (int b = 0; b < 32; ++b)
-                        if ((iw >> b) & 1u) {
-                            const float v = ((vw >> b) & 1u) ? -1.0f : 1.0f;
-                            if (cm) cm[k] = alive ? v : 0.0f;
-                            if (mh) mh[k] = v;
-                            ++k;
-                        }
-                }
-        }
+        list_finish(a, bw, met, ls, cw, cwc, valid, half, slot, base);
     }
 }
 
@@ -378,9 +209,11 @@ static int launch_list(const ListArgs& a, hipStream_t s) {
 
 using namespace npd;
 
-// the handles the list kernel covers: the fp32 LDS-resident GRU kernel's (F 32 or 64, plain Linear head)
+// the handles the list kernels cover: fp32 GRU cells with a plain Linear head, on the LDS-resident kernel (F 32 or 64)
+// or the weight-streaming one (F 256 or 512; F = 128 is not instantiated)
 static bool list_handle_ok(const npd_gru* g) {
-    return g->cell == 0 && g->precision == 0 && (g->F == 32 || g->F == 64) && g->ln == 0 && g->hd == nullptr;
+    return g->cell == 0 && g->precision == 0 && (g->F == 32 || g->F == 64 || g->F == 256 || g->F == 512) && g->ln == 0 &&
+           g->hd == nullptr;
 }
 
 extern "C" int npd_gru_list_supported(const npd_gru* gru, const npd_code* code, int list_size) {
@@ -397,8 +230,8 @@ extern "C" int npd_gru_list_decode(const npd_gru* g, const npd_code* code, const
     NPD_ARG(list_size >= 1 && list_size <= 8, "npd_gru_list_decode: list_size must be 1 .. 8");
     NPD_ARG(code->p.N == g->N, "npd_gru_list_decode: the code's N differs from the GRU handle's");
     if (!list_handle_ok(g))
-        return fail(NPD_ENOTSUP, "npd_gru_list_decode: list decoding runs on the fp32 GRU kernel (GRU cell, precision 0, "
-                                 "F 32 or 64, plain Linear head)");
+        return fail(NPD_ENOTSUP, "npd_gru_list_decode: list decoding runs on the fp32 GRU kernels (GRU cell, precision 0, "
+                                 "F 32, 64, 256 or 512, plain Linear head)");
     if (B == 0) return NPD_OK;
     NPD_ARG(msg_hat != nullptr || cand_msg != nullptr, "npd_gru_list_decode: msg_hat and cand_msg both NULL");
     NPD_ARG(y != nullptr, "npd_gru_list_decode: y is NULL");
@@ -428,6 +261,7 @@ extern "C" int npd_gru_list_decode(const npd_gru* g, const npd_code* code, const
     for (int i = 0; i < g->N; ++i)
         if (!((code->p.frozen[i >> 5] >> (i & 31)) & 1u)) a.info[i >> 5] |= 1u << (i & 31);
     hipStream_t s = (hipStream_t)stream;
+    if (g->F > 64) return gru::launch_wide_list(g, a, s);
     return gru::dispatch(gru::NarrowShapes{}, [&](auto f, auto l) { return gru::launch_list<f.value, l.value>(a, s); },
                          g->F, g->layers);
 }

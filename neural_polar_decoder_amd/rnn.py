@@ -363,8 +363,9 @@ class RNN_decoder:
             return "list_decode does not cover the LayerNorm head (--use_layernorm)"
         if getattr(net, "out_linear_depth", 1) != 1:
             return "list_decode does not cover out_linear_depth > 1 heads"
-        if net.feature_size not in (32, 64):
-            return f"list_decode runs on the LDS-resident fp32 kernel: feature_size 32 or 64, got {net.feature_size}"
+        if net.feature_size not in (32, 64, 256, 512):
+            return ("list_decode runs on the fp32 list kernels (weights in LDS or streamed): feature_size 32, 64, 256 or "
+                    f"512, got {net.feature_size}")
         if not isinstance(L, (int, np.integer)) or not 1 <= int(L) <= self.MAX_LIST:
             return f"list size L must be an integer in 1 .. {self.MAX_LIST}, got {L!r}"
         if not (hasattr(net, "fused_supported") and net.fused_supported("y_input", "fp32", self.N)):
@@ -379,7 +380,9 @@ class RNN_decoder:
         """rnn_all.RNN_decoder.list_decode (rnn_all.py:580-664) in one fused launch (npd_gru_list_decode): the (B, K)
         +-1 messages of the list survivor nearest to y.  `code` is this package's PolarCode or PAC (its information set
         and encoder drive the final selection).  return_candidates: also (cand_msg (B, L, K), cand_metric (B, L),
-        sel (B) int32) -- the final list in the reference's order; unused slots (2^K < L) hold metric +inf, message 0."""
+        sel (B) int32) -- the final list in the reference's order; unused slots (2^K < L) hold metric +inf, message 0.
+        Unidirectional fp32 GRU nets with the plain Linear head at feature_size 32 / 64 (weights in LDS) and 256 / 512
+        (weights streamed, the greedy decoder's N limit); list_supported(net, L) tells beforehand."""
         why = self._list_reason(net, L)
         if why is not None:
             raise _lib.NpdError(why)

@@ -1,16 +1,19 @@
 """GRU list decoding throughput on cuda:0 (npd_gru_list_decode) beside the greedy decoder and a torch restatement.
 
-    python tools/rnnl_bench.py [--out FILE.json] [--quick]
+    python tools/rnnl_bench.py [--case f64|f512] [--out FILE.json] [--quick]
 
-One configuration: Polar(64,32), a seeded hidden-64, 2-layer GRU (onehot y_input), fp32, B = 2^18 words at 2 dB, list
-sizes L = 1, 2, 4, 8.  After two warm-up calls every leg is timed with device events around single calls, REPS times;
+Two configurations, one per run, both seeded 2-layer GRUs (onehot y_input), fp32, at 2 dB, list sizes L = 1, 2, 4, 8:
+  f64   Polar(64,32), hidden 64 (gru_list_kernel, weights in LDS), B = 2^18 words, torch on 2^14;
+  f512  Polar(64,22), hidden 512 (gru_wide_list_kernel, weights streamed; the CRISP recipe's shape), B = 2^15 words,
+        torch on 2^13.
+After two warm-up calls every leg is timed with device events around single calls, REPS times;
 reported are the median, the minimum and the maximum.  In the same run, on the same words:
   * greedy: RNN_decoder.decode's kernel (npd_gru_decode, fp32).  A wave of the list kernel holds 1 / Lp as many
     codewords (Lp = L rounded up to 1, 2, 4, 8), so the expectation is list time ~ Lp x greedy time; the ratio
     list / (Lp x greedy) is printed per L.
   * torch: the list loop of rnn_all.py:580-664 restated with this package's RNN_Model on the GPU (all live paths of all
-    words as one batch per step, topk + sort + gather for the pruning), on 2^14 words -- what a user has without the
-    kernel.
+    words as one batch per step, topk + sort + gather for the pruning), on fewer words (above) -- what a user has
+    without the kernel.
 Rates: codewords/s; FLOP/s = 2 x (N (9 F^2) + 3 F N) MACs per path and word (the three GRU GEMMs per step and the y
 projection; L = 1 counts one path, the list kernel computes Lp) over the median time, as a fraction of the fp32 MFMA
 peak (157.3 TFLOP/s, the spec figure at 2.4 GHz).  The held clock is sampled with `rocm-smi --showclocks` while the L = 8
@@ -35,7 +38,11 @@ from neural_polar_decoder_amd.rnn import get_onehot  # noqa: E402
 PEAK_FP32 = 157.3e12
 REPS = 10
 SNR = 2.0
-N, K, F, LAYERS = 64, 32, 64, 2
+CASES = {  # name: (N, K, F, layers, log2 B, log2 B of the torch leg)
+    "f64": (64, 32, 64, 2, 18, 14),
+    "f512": (64, 22, 512, 2, 15, 13),
+}
+N, K, F, LAYERS = CASES["f64"][:4]
 
 
 def time_call(fn, reps=REPS):
@@ -110,20 +117,23 @@ class ClockSampler(threading.Thread):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--case", choices=list(CASES), default="f64")
     ap.add_argument("--out", default=None)
     ap.add_argument("--quick", action="store_true", help="1/16 of the batches (a rehearsal, not a measurement)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("rnnl_bench needs the GPU: there is no CPU path to time")
     dev = torch.device("cuda:0")
+    global N, K, F, LAYERS
+    N, K, F, LAYERS, lb, lbt = CASES[a.case]
     q = 16 if a.quick else 1
-    B, Bt = (1 << 18) // q, (1 << 14) // q
+    B, Bt = (1 << lb) // q, (1 << lbt) // q
     code = npd.reference_polar_code(N, K)
     info = np.sort(np.asarray(code.info_positions))
     net, dec = seeded_crisp(code, F, LAYERS, seed=0, device=dev)
     _, _, y = code.mc_generate(B, SNR, seed=1, device=dev, want_msg=False)
     flop_path = 2.0 * (N * 9 * F * F + 3 * F * N)
-    rec = {"code": f"polar({N},{K})", "F": F, "layers": LAYERS, "B": B, "snr_db": SNR, "reps": REPS}
+    rec = {"case": a.case, "code": f"polar({N},{K})", "F": F, "layers": LAYERS, "B": B, "snr_db": SNR, "reps": REPS}
 
     tg, lo, hi = time_call(lambda: dec.decode(net, False, y))
     rec["greedy"] = {"s_per_call": tg, "min": lo, "max": hi, "cw_per_s": B / tg,
