@@ -147,11 +147,26 @@ int npd_sc_decode_soft_new(const npd_code* code, const float* y, float llr_scale
  * LLRs), path metric += |leaf| on a frozen leaf with sign(leaf) != 1 and on the flipped branch of an
  * information leaf; survivors = torch.topk's choice (ties resolved exactly as std::nth_element, see
  * npd_list_prune_select) in list order; final path = the first minimum of ||encode(u) - y||^2.
- * Polar codes, 8 <= N <= 256, 1 <= list_size <= 8, y 16-byte aligned.  Outputs: msg_hat (B,K) and
+ * Polar and PAC codes, 8 <= N <= 256, 1 <= list_size <= 8, y 16-byte aligned.  Outputs: msg_hat (B,K) and
  * u_hat (B,N) of the chosen path, each optional.  scl_decode's leaf-LLR output equals
  * npd_sc_decode(..., gt = u_hat) (a genie pass reproduces the chosen path's LLRs bit for bit).
  * Decisions are bit-exact with the reference except when two list candidates' fp32 distances differ
  * only by summation order (torch's vectorised sum vs a sequential one here).
+ *
+ * PAC handles (pac_g > 1; the reference has no PAC list decoder, so this defines one): the same list decoder with
+ * its leaf step replaced by pac_sc_decode's (pac_code.py:534-573); no priors.  Every path also carries its
+ * convolution state, the last len(g_array) - 1 values of v_hat, initially all +1; u0 = conv1bTrans(+1, state) is the
+ * product of the tapped state entries (conv1bTrans(-1, state) = -u0).
+ *   frozen position:      v = +1, u = u0, the state advances with +1; metric = fl32(m + |l|) if sign(l) != u0
+ *                         (sign(0) = 0 counts as unequal, the penalty is then 0), else m; no fork.
+ *   information position: every path forks, in list order, into [keep_0 .. keep_{s-1}, flip_0 .. flip_{s-1}]; keep has
+ *                         u = sign(l), metric m; flip has u = -sign(l), metric fl32(m + |l|); v = u * u0 advances the
+ *                         state; l == 0 gives u = v = 0 in both children and the state does not advance.  More than
+ *                         list_size children are pruned as above.
+ *   final path:           the first minimum over the live list of ||polar_encode(u) - y||^2 (fp32, summed sequentially).
+ * For PAC msg_hat is v_hat[:, B] and u_hat is the convolved word u; the fused counts of npd_scl_decode_mc compare
+ * v_hat[:, B] with the Philox message (a 0 counts as an error).  list_size = 1 is pac_sc_decode bit for bit; pac_g = 2
+ * (no tap, u = v) gives Polar SC-List's decisions.
  */
 int npd_scl_decode(const npd_code* code, const float* y, float llr_scale, int list_size, float* msg_hat,
                    float* u_hat, int64_t B, void* stream);

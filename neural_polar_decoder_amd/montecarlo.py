@@ -135,8 +135,9 @@ class SCMonteCarlo(MonteCarlo):
 
 
 class SCLMonteCarlo(SCMonteCarlo):
-    """Polar SC-List decoding (polar.py:793-876, run_models.py:327-331): fused generate +
-    npd_scl_decode_mc (decode and count in one launch)."""
+    """SC-List decoding of a PolarCode (polar.py:793-876, run_models.py:327-331) or a PAC (the same list decoder
+    with pac_sc_decode's leaf step, PAC.pac_scl_decode): generate + npd_scl_decode_mc (decode and count in one
+    launch; for PAC the counts compare v_hat[:, B] with the message)."""
 
     def __init__(self, code, list_size, snrs, total_cw, batch, seed=1234, rank=None, world=None, device=None):
         super().__init__(code, snrs, total_cw, batch, seed, rank, world, device, fused=False)
@@ -330,7 +331,7 @@ def _parse_args(argv=None):
     ap.add_argument("--test_size", type=int, default=1 << 20)
     ap.add_argument("--batch_size", type=int, default=1 << 20)
     ap.add_argument("--seed", type=int, default=1234)
-    ap.add_argument("--list_size", type=int, default=None, help="also run SC-List with this list size (Polar)")
+    ap.add_argument("--list_size", type=int, default=None, help="also run SC-List with this list size, 1 .. 8 (Polar and PAC)")
     ap.add_argument("--lse", action="store_true", help="also run the exact-LSE sc_decode (Polar, polar.py:209)")
     ap.add_argument("--hard_decision", action="store_true", help="exact-LSE SC with sign decisions (else tanh)")
     ap.add_argument("--ml", action="store_true", help="also run maximum-likelihood decoding over the codebook "
@@ -380,8 +381,6 @@ def _main(argv=None):
     res = SCMonteCarlo(code, snrs, a.test_size, a.batch_size, a.seed).run()
     scl = None
     if a.list_size:
-        if a.code != "polar":
-            raise SystemExit("--list_size: SC-List is defined for Polar codes only (polar.py:793)")
         scl = SCLMonteCarlo(code, a.list_size, snrs, a.test_size, a.batch_size, a.seed).run()
     lse = None
     if a.lse:

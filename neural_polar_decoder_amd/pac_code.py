@@ -131,6 +131,58 @@ class PAC:
         c = corrupted_codewords
         return _lib.home(llr, c), _lib.home(vh, c), _lib.home(uh, c)
 
+    # ------------------------------------------------------------------ SC-List
+    def pac_scl_decode(self, corrupted_codewords, snr, L=1, want_llrs=True):
+        """SC-List decoding of the PAC code; returns (leaf LLRs of the chosen path (B,N), v_hat[:, B] (B,K),
+        u_hat (B,N)), the shape of pac_sc_decode's return.
+
+        The reference has no PAC list decoder: this is PolarCode.scl_decode (polar.py:793-876, use_CRC=False)
+        with pac_sc_decode's leaf step (pac_code.py:534-573).  Every path carries its convolution state; a frozen
+        leaf decides u = u0 = conv1bTrans(+1, state) and pays |l| unless sign(l) == u0; an information leaf forks
+        into u = sign(l) (metric m) and u = -sign(l) (metric m + |l|) with v = u * u0, and l == 0 gives u = v = 0
+        without advancing the state; more than L children are pruned as pruneLists does (torch.topk); the final
+        path is the first minimum of ||polar_encode(u) - y||^2.  L = 1 is pac_sc_decode.  The leaf LLRs come from a
+        genie SC pass with the chosen u_hat (identical values); ``want_llrs=False`` skips it and returns None."""
+        y = _aligned(_lib.f32c(_lib.stage(corrupted_codewords, "corrupted_codewords")))
+        Bn = y.shape[0]
+        h = self._code_for(self.B)
+        vh = torch.empty(Bn, h.K, dtype=torch.float32, device=y.device)
+        uh = torch.empty(Bn, self.N, dtype=torch.float32, device=y.device)
+        st = _lib.stream_of(y.device)
+        _lib.check(_lib.load().npd_scl_decode(h.h, _lib.ptr(y), llr_scale(snr), int(L), _lib.ptr(vh), _lib.ptr(uh), Bn,
+                                              st), "npd_scl_decode")
+        c = corrupted_codewords
+        if not want_llrs:
+            return None, _lib.home(vh, c), _lib.home(uh, c)
+        llr = torch.empty(Bn, self.N, dtype=torch.float32, device=y.device)
+        _lib.check(_lib.load().npd_sc_decode(h.h, _lib.ptr(y), llr_scale(snr), _lib.ptr(llr), None, None, _lib.ptr(uh),
+                                             Bn, st), "npd_sc_decode (genie leaf LLRs)")
+        return _lib.home(llr, c), _lib.home(vh, c), _lib.home(uh, c)
+
+    def scl_decode(self, corrupted_codewords, snr, L=1, use_CRC=False, want_llrs=True):
+        """PolarCode.scl_decode's signature and return for a PAC code: (leaf LLRs of the chosen path (B,N) or
+        None, msg_hat = v_hat[:, B] (B,K)) of pac_scl_decode."""
+        if use_CRC:
+            raise NotImplementedError("scl_decode(use_CRC=True) depends on module globals of the reference "
+                                      "(polar.py:741-763: `polar.CRC_len`); only the use_CRC=False path is built")
+        llr, vh, _ = self.pac_scl_decode(corrupted_codewords, snr, L, want_llrs)
+        return llr, vh
+
+    def scl_decode_mc(self, y, snr, L, seed, cw_offset, counters, msg_hat=None):
+        """counters += {bit errors, block errors} of pac_scl_decode's v_hat[:, B] against the Philox messages of
+        codewords cw_offset .. cw_offset + batch - 1 (decode and count in one launch, as PolarCode.scl_decode_mc)."""
+        _lib.require_gpu(y, "y")
+        if y.dim() != 2 or y.shape[1] != self.N:
+            raise ValueError(f"y must be (batch, {self.N}), got {tuple(y.shape)}")
+        h = self._code_for(self.B)
+        _lib.check_out(counters, "counters", torch.int64, 2, y.device)
+        _lib.check_out(msg_hat, "msg_hat", torch.float32, y.shape[0] * h.K, y.device, optional=True)
+        y = _aligned(_lib.f32c(y))
+        _lib.check(_lib.load().npd_scl_decode_mc(h.h, _lib.ptr(y), llr_scale(snr), int(L), _lib.ptr(msg_hat),
+                                                 int(seed), int(cw_offset), y.shape[0], _lib.ptr(counters),
+                                                 _lib.stream_of(y.device)), "npd_scl_decode_mc")
+        return counters
+
     def extract(self, v_hat, B=None):
         if B is None:
             B = self.B
