@@ -62,7 +62,7 @@ struct ArgsB {
     unsigned long long* counters;
     int K;
     int nseg;
-    uint32_t slotw[kMaxN / 4];  // byte jj & 3 of word jj >> 2 = slot of position jj (scalar-loaded per step)
+    uint32_t slotw[kMaxN / 4];  // byte jj & 3 of word jj >> 2 = slot of position jj (copied to the LDS step table)
 };
 
 static uint16_t bf16_rne(float f) {

@@ -30,6 +30,9 @@ struct Geo16 {
     static constexpr int OFF_C = 2 * IMG4 * 4;       // floats: constants after the weight fragments
     static constexpr int C0L0 = OFF_C, C1L0 = OFF_C + 192, BHN0 = OFF_C + 384, C0L1 = OFF_C + 448,
                          BHN1 = OFF_C + 640, WLIN = OFF_C + 704, TOTAL = OFF_C + 768;
+    // behind the image in LDS, written by every block from the kernel arguments: one word per step in DECODE order
+    // (rev applied), bits 0-7 the position's message slot (255: not compared), bit 8 its is-information bit
+    static constexpr int LDS_BYTES = TOTAL * 4 + kMaxN * 4;
 };
 
 __device__ __forceinline__ f4 mfma16s(const hf8& a, const hf8& b, const f4& c) {
@@ -83,6 +86,16 @@ __device__ __forceinline__ f4 fma4(float x, const f4& c, const f4& p) {
 // element i, stage 0 exp2s / 1 rcps + n-gate input + exp2 / 2 rcp + blend), spread over its MFMA triples between
 // sched_barrier fences; the h1 update of tile 3, the output, the decision and the h1 split ride on the NEXT step's
 // layer-0 tile-0 GEMM (which needs only h0', not x_i: the x_i column and P are added after it).
+// What follows that GEMM's last MFMA has no MFMA of this wave to ride on, so the count-only body (CNT) keeps it
+// short (instruction counts per path: profiles/round7/gru16_strip_ab.txt):
+//  - no scalar memory load in the step loop: the position's message slot and is-information bit come from a table
+//    in LDS (Geo16::LDS_BYTES), read with one wave-uniform ds_read a GEMM ahead.  SMEM returns out of order, so a
+//    wait for it was an lgkmcnt(0) that also drained the `cur` fragment look-ahead;
+//  - the x_i columns the top of the step needs are read beside the tail GEMM, not at the top;
+//  - CNT computes the output, its row reduction and the sign only at information positions: a frozen position's
+//    decision is the constant 1.0.
+// The h1 split stays after the decision: splitting each finished h1 tile beside a later layer-1 GEMM (results pinned
+// with empty asm, or the compiler sinks them back) measured 0.25 % slower than leaving it there (same file).
 template <int SPLIT>
 struct Upd4 {
     f4 er, ez, en, z;
@@ -165,16 +178,25 @@ __device__ __forceinline__ void gemm16i(const f4* __restrict__ smem4, uint32_t w
     });
 }
 
-template <int SPLIT>
+// CNT: the count-only body (counters != NULL; decoded, logits, gt and h0 all NULL): no decision store, no genie load,
+// and at a frozen position the decision is the constant 1.0 without the output having been computed.
+template <int SPLIT, bool CNT>
 __global__ __launch_bounds__(64 * NPD_GRU16_WPB) void gru16p_kernel(const ArgsB a) {
     using G = Geo16;
     using S = SplitT<SPLIT>;
     using V = typename S::V;
     using E = typename S::E;
     extern __shared__ __attribute__((aligned(16))) f4 smem4[];
+    const uint32_t* tab = reinterpret_cast<const uint32_t*>(smem4) + G::TOTAL;
     {
         const f4* src = reinterpret_cast<const f4*>(a.img);
         for (int i = threadIdx.x; i < G::TOTAL / 4; i += blockDim.x) smem4[i] = src[i];
+        uint32_t* tw = reinterpret_cast<uint32_t*>(smem4) + G::TOTAL;
+        for (int i = threadIdx.x; i < a.N; i += blockDim.x) {
+            const int jj = a.rev ? a.N - 1 - i : i;
+            const uint32_t sl = a.counters ? (a.slotw[jj >> 2] >> (8 * (jj & 3))) & 255u : 255u;
+            tw[i] = sl | (((a.info[jj >> 5] >> (jj & 31)) & 1u) << 8);
+        }
         __syncthreads();
     }
     const int lane = threadIdx.x & 63;
@@ -213,19 +235,33 @@ __global__ __launch_bounds__(64 * NPD_GRU16_WPB) void gru16p_kernel(const ArgsB 
         const int64_t rowoff = (seg * a.B + cw) * N;       // this codeword's row of y / decoded / logits
         // count mode: the codeword's messages as 2-bit codes of rint(msg) (-1: 0, +1: 1, 0: 2, else 3; the decision
         // d is in {-1, 0, +1}), slot sl held by row sl & 3 at bits 2 (q & 15) of word q >> 4, q = sl >> 2: 4 registers
-        // cover K <= 256, loaded once per tile, so no step waits on a message load
+        // cover K <= 256, loaded once per tile, so no step waits on a message load.  Eight slots of a row form a group
+        // behind one wave-uniform bound; inside it the index is clamped instead of guarded, so the group's eight
+        // loads are in flight together (K = 32: one round trip per tile)
         uint32_t mc[4] = {0u, 0u, 0u, 0u};
         if (count) {
             const float* mr = a.msg + cwc * a.K;
+            int g4t = g4;  // laundered per tile: the clamped indices are not to be hoisted out of the tile loop
+            asm volatile("" : "+v"(g4t));
 #pragma unroll
             for (int w = 0; w < 4; ++w)
-                for (int j = 0; j < 16; ++j) {
-                    const int sl = 4 * (16 * w + j) + g4;
-                    if (sl >= a.K) break;
-                    const float v = rintf(mr[sl]);
-                    const uint32_t code = v == -1.0f ? 0u : v == 1.0f ? 1u : v == 0.0f ? 2u : 3u;
-                    mc[w] |= code << (2 * j);
-                }
+#pragma unroll
+                for (int j0 = 0; j0 < 16; j0 += 8)
+                    if (4 * (16 * w + j0) < a.K) {
+                        float mv[8];
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) {
+                            const int sl = 4 * (16 * w + j0 + j) + g4t;
+                            mv[j] = mr[sl < a.K ? sl : a.K - 1];
+                        }
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) {
+                            const int sl = 4 * (16 * w + j0 + j) + g4t;
+                            const float v = rintf(mv[j]);
+                            const uint32_t code = v == -1.0f ? 0u : v == 1.0f ? 1u : v == 0.0f ? 2u : 3u;
+                            mc[w] |= (sl < a.K ? code : 0u) << (2 * (j0 + j));
+                        }
+                    }
         }
         uint32_t nerr = 0;  // this row's share of the codeword's bit errors
         f4 P[G::RT];
@@ -243,14 +279,21 @@ __global__ __launch_bounds__(64 * NPD_GRU16_WPB) void gru16p_kernel(const ArgsB 
                     yh[j] = (E)v;
                     if (S::kLo) yl[j] = (E)(v - (float)yh[j]);
                 }
+                // the K block's weight fragments, all requested before the first MFMA (states, B fragments and the
+                // step's accumulators are not live yet): one L2 round trip per K block, not one per row tile
+                V wh[G::RT], wl[G::RT];
 #pragma unroll
                 for (int t = 0; t < G::RT; ++t) {
-                    const V wh = __builtin_bit_cast(V, a.wy[(t * nkb + kb) * 64 + lane]);
-                    P[t] = mfma16s(wh, yh, P[t]);
+                    wh[t] = __builtin_bit_cast(V, a.wy[(t * nkb + kb) * 64 + lane]);
+                    if (S::kLo) wl[t] = __builtin_bit_cast(V, a.wy[a.wy_lo + (t * nkb + kb) * 64 + lane]);
+                }
+                asm volatile("" ::: "memory");
+#pragma unroll
+                for (int t = 0; t < G::RT; ++t) {
+                    P[t] = mfma16s(wh[t], yh, P[t]);
                     if (S::kLo) {
-                        const V wl = __builtin_bit_cast(V, a.wy[a.wy_lo + (t * nkb + kb) * 64 + lane]);
-                        P[t] = mfma16s(wh, yl, P[t]);
-                        P[t] = mfma16s(wl, yh, P[t]);
+                        P[t] = mfma16s(wh[t], yl, P[t]);
+                        P[t] = mfma16s(wl[t], yh, P[t]);
                     }
                 }
             }
@@ -261,7 +304,7 @@ __global__ __launch_bounds__(64 * NPD_GRU16_WPB) void gru16p_kernel(const ArgsB 
             h0[t] = zero;
             h1[t] = zero;
         }
-        if (a.h0) {  // register e of tile t = hidden unit 16 t + 4 g4 + e of codeword col (F = 64, 2 layers)
+        if (!CNT && a.h0) {  // register e of tile t = hidden unit 16 t + 4 g4 + e of codeword col (F = 64, 2 layers)
             const float* hr = a.h0 + (seg * a.B + cwc) * 128;
 #pragma unroll
             for (int t = 0; t < 4; ++t)
@@ -282,19 +325,22 @@ __global__ __launch_bounds__(64 * NPD_GRU16_WPB) void gru16p_kernel(const ArgsB 
         Frag16<SPLIT, 3> cur;
         load_kb16<SPLIT, 3>(smem4, wbs[0], T0, 0, cur);
         gemm16i<SPLIT, 3, 0, 0>(smem4, wbs[0], T0, a0, fh, fl, cur, wbs[0], T1, nowork);
+        // the x_i columns of hidden tile 0 and of tile 1's r and z rows (the step's first GEMM), read a GEMM ahead
+        // (here, then beside the tail GEMM): the top of the step, which has no MFMA of this wave to hide behind, does
+        // not start on an LDS round trip.  Tile 1's: count-only (the general body has no registers to hold them
+        // across the tail: it spills with them)
+        constexpr int NX = CNT ? 5 : 3;
+        f4 xc[5] = {c4(G::C1L0, 0), c4(G::C1L0, 4), c4(G::C1L0, 8), c4(G::C1L0, 1), c4(G::C1L0, 5)};
         for (int ii = 0; ii < N; ++ii) {
-            const int jj = a.rev ? N - 1 - ii : ii;
             Upd4<SPLIT> u;
-            // count mode: this step's message slot (255: not compared), from the kernel arguments by a scalar load
-            const int sl = count ? (int)((a.slotw[jj >> 2] >> (8 * (jj & 3))) & 255u) : 255;
             // ================= layer 0
-            f4 ap[3] = {a0[0] + fma4(xb, c4(G::C1L0, 0), P[0]), a0[1] + fma4(xb, c4(G::C1L0, 4), P[4]), a0[2]};
-            f4 ainp = fma4(xb, c4(G::C1L0, 8), P[8]);
+            f4 ap[3] = {a0[0] + fma4(xb, xc[0], P[0]), a0[1] + fma4(xb, xc[1], P[4]), a0[2]};
+            f4 ainp = fma4(xb, xc[2], P[8]);
             static_for<1, 4>([&](auto htc) {
                 constexpr int ht = decltype(htc)::value;
                 const int T[3] = {ht, 4 + ht, 8 + ht};
-                f4 acc[3] = {fma4(xb, c4(G::C1L0, ht), P[ht]), fma4(xb, c4(G::C1L0, 4 + ht), P[4 + ht]),
-                             c4(G::BHN0, ht)};
+                f4 acc[3] = {fma4(xb, (ht == 1 && NX == 5) ? xc[3] : c4(G::C1L0, ht), P[ht]),
+                             fma4(xb, (ht == 1 && NX == 5) ? xc[4] : c4(G::C1L0, 4 + ht), P[4 + ht]), c4(G::BHN0, ht)};
                 constexpr int TN[3] = {ht < 3 ? ht + 1 : 0, ht < 3 ? 5 + ht : 4, ht < 3 ? 9 + ht : 8};
                 gemm16i<SPLIT, 3, 0, 12>(smem4, wbs[0], T, acc, fh, fl, cur, wbs[ht < 3 ? 0 : 2], TN, [&](auto cc) {
                     u.template step<decltype(cc)::value>(h0[ht - 1], ap[0], ap[1], ainp, ap[2]);
@@ -318,11 +364,13 @@ __global__ __launch_bounds__(64 * NPD_GRU16_WPB) void gru16p_kernel(const ArgsB 
                 constexpr int ht = decltype(htc)::value;
                 const int T[3] = {ht, 4 + ht, 8 + ht};
                 f4 bb[3] = {c4(G::C0L1, ht), c4(G::C0L1, 4 + ht), c4(G::BHN1, ht)};
+                // chunks 0-11: h1 tile ht - 1's update; 12: its output terms (count-only: in the decision chunk, where
+                // the position is an information one)
                 auto work = [&](auto cc) {
                     constexpr int c = decltype(cc)::value;
                     if constexpr (c < 12) {
                         u.template step<c>(h1[ht - 1], q[0], q[1], q[2], q[3]);
-                    } else {
+                    } else if constexpr (!CNT) {
                         const f4 wl = c4(G::WLIN, ht - 1);
 #pragma unroll
                         for (int i = 0; i < 4; ++i) part = fmaf(wl[i], h1[ht - 1][i], part);
@@ -337,8 +385,13 @@ __global__ __launch_bounds__(64 * NPD_GRU16_WPB) void gru16p_kernel(const ArgsB 
                 q[2] = bbi[2];
                 q[3] = bb[2];
             });
-            // ================= tail: next step's layer-0 tile-0 GEMM beside h1 tile 3's update, the output, the
-            // decision and the h1 split
+            // ================= tail: next step's layer-0 tile-0 GEMM beside h1 tile 3's update, the decision and the
+            // h1 split.  This step's table word is read here, a GEMM ahead of the decision: LDS returns in order, so
+            // its wait is a counted one behind the `cur` look-ahead
+            const uint32_t tv = tab[ii];
+            uint32_t te = 0u;
+#pragma unroll
+            for (int k = 0; k < NX; ++k) xc[k] = c4(G::C1L0, k < 3 ? 4 * k : 4 * k - 11);
             a0[0] = zero;
             a0[1] = zero;
             a0[2] = c4(G::BHN0, 0);
@@ -346,24 +399,42 @@ __global__ __launch_bounds__(64 * NPD_GRU16_WPB) void gru16p_kernel(const ArgsB 
                 constexpr int c = decltype(cc)::value;
                 if constexpr (c < 12) {
                     u.template step<c>(h1[3], q[0], q[1], q[2], q[3]);
+                    if constexpr (c == 10) te = __builtin_amdgcn_readfirstlane(tv);
                 } else if constexpr (c == 12) {
-                    const f4 wl = c4(G::WLIN, 3);
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) part = fmaf(wl[i], h1[3][i], part);
-                    const float out = sum_rows16(part) + a.b_lin;
-                    const bool info = (a.info[jj >> 5] >> (jj & 31)) & 1u;
+                    const bool info = (te >> 8) & 1u;
+                    const uint32_t sl = te & 255u;  // message slot (255: not compared)
                     float d;
-                    if (info) d = out > 0.0f ? 1.0f : (out < 0.0f ? -1.0f : 0.0f);
-                    else d = a.gt ? a.gt[(seg * a.B + cwc) * N + jj] : 1.0f;
-                    if (g4 == 0 && valid) {
-                        if (a.decoded) a.decoded[rowoff + jj] = d;
-                        if (a.logits) a.logits[rowoff + ii] = out;
+                    if constexpr (CNT) {
+                        d = 1.0f;  // a frozen position's decision: no output, no reduction, no sign test
+                        if (info) {
+#pragma unroll
+                            for (int t = 0; t < 4; ++t) {
+                                const f4 wl = c4(G::WLIN, t);
+#pragma unroll
+                                for (int i = 0; i < 4; ++i) part = fmaf(wl[i], h1[t][i], part);
+                            }
+                            const float out = sum_rows16(part) + a.b_lin;
+                            d = out > 0.0f ? 1.0f : (out < 0.0f ? -1.0f : 0.0f);
+                        }
+                    } else {
+                        const int jj = a.rev ? N - 1 - ii : ii;
+                        const f4 wl = c4(G::WLIN, 3);
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) part = fmaf(wl[i], h1[3][i], part);
+                        const float out = sum_rows16(part) + a.b_lin;
+                        if (info) d = out > 0.0f ? 1.0f : (out < 0.0f ? -1.0f : 0.0f);
+                        else d = a.gt ? a.gt[(seg * a.B + cwc) * N + jj] : 1.0f;
+                        if (g4 == 0 && valid) {
+                            if (a.decoded) a.decoded[rowoff + jj] = d;
+                            if (a.logits) a.logits[rowoff + ii] = out;
+                        }
                     }
-                    if (sl != 255) {  // count_errors_kernel's test, rint(msg) != rint(d), on the 2-bit codes
-                        const int q = sl >> 2, w = q >> 4;
-                        const uint32_t mw = w == 0 ? mc[0] : w == 1 ? mc[1] : w == 2 ? mc[2] : mc[3];
+                    if (sl != 255u) {  // count_errors_kernel's test, rint(msg) != rint(d), on the 2-bit codes
+                        const uint32_t q = sl >> 2;
+                        const uint32_t m01 = (q & 16u) ? mc[1] : mc[0], m23 = (q & 16u) ? mc[3] : mc[2];
+                        const uint32_t mw = (q & 32u) ? m23 : m01;
                         const uint32_t dc = d > 0.0f ? 1u : (d < 0.0f ? 0u : 2u);
-                        nerr += (g4 == (sl & 3) && ((mw >> (2 * (q & 15))) & 3u) != dc) ? 1u : 0u;
+                        nerr += (g4 == (sl & 3u) && ((mw >> (2 * (q & 15u))) & 3u) != dc) ? 1u : 0u;
                     }
                     const float sd = d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f);
                     xb = a.onehot ? (sd > 0.0f ? 1.0f : 0.0f) : sd;
@@ -455,9 +526,15 @@ void build_image_split16(npd_gru& g, const float* W, HostImages& im) {
 int launch_split16(const npd_gru* g, const ArgsB& b, hipStream_t s) {
     const int64_t tiles = (b.B + 15) / 16 * (b.nseg > 1 ? b.nseg : 1);
     const int grid = grid_for((tiles + NPD_GRU16_WPB - 1) / NPD_GRU16_WPB, 1, device_cu_count());
+    // counting with nothing else to read or write: the count-only body
+    if (b.counters && !b.decoded && !b.logits && !b.gt && !b.h0)
+        return dispatch(Split16s{}, [&](auto sp) {
+            return launch_lds<gru16p_kernel<sp.value, true>>("gru16p_kernel launch (count-only)", grid,
+                                                             64 * NPD_GRU16_WPB, Geo16::LDS_BYTES, s, b);
+        }, g->split16);
     return dispatch(Split16s{}, [&](auto sp) {
-        return launch_lds<gru16p_kernel<sp.value>>("gru16p_kernel launch", grid, 64 * NPD_GRU16_WPB,
-                                                   (size_t)Geo16::TOTAL * 4, s, b);
+        return launch_lds<gru16p_kernel<sp.value, false>>("gru16p_kernel launch", grid, 64 * NPD_GRU16_WPB,
+                                                          Geo16::LDS_BYTES, s, b);
     }, g->split16);
 }
 
