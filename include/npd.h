@@ -147,7 +147,8 @@ int npd_sc_decode_soft_new(const npd_code* code, const float* y, float llr_scale
  * LLRs), path metric += |leaf| on a frozen leaf with sign(leaf) != 1 and on the flipped branch of an
  * information leaf; survivors = torch.topk's choice (ties resolved exactly as std::nth_element, see
  * npd_list_prune_select) in list order; final path = the first minimum of ||encode(u) - y||^2.
- * Polar and PAC codes, 8 <= N <= 256, 1 <= list_size <= 8, y 16-byte aligned.  Outputs: msg_hat (B,K) and
+ * Polar and PAC codes, 8 <= N <= 256, 1 <= list_size <= 32 (any value, not only powers of two; the live list is
+ * min(2^bits decided, list_size) paths, the final one min(2^K, list_size)), y 16-byte aligned.  Outputs: msg_hat (B,K) and
  * u_hat (B,N) of the chosen path, each optional.  scl_decode's leaf-LLR output equals
  * npd_sc_decode(..., gt = u_hat) (a genie pass reproduces the chosen path's LLRs bit for bit).
  * Decisions are bit-exact with the reference except when two list candidates' fp32 distances differ
@@ -179,6 +180,8 @@ int npd_scl_decode_mc(const npd_code* code, const float* y, float llr_scale, int
  * survives.  The same code runs inside the SCL kernel when metrics tie across the boundary.
  */
 int npd_list_prune_select(const float* neg_metrics, int n, int keep, uint32_t* mask_out);
+/* The same for 1 <= keep <= n <= 64 candidates (list sizes 9 .. 32 prune up to 64), as a 64-bit mask. */
+int npd_list_prune_select64(const float* neg_metrics, int n, int keep, uint64_t* mask_out);
 
 /*
  * A whole SNR sweep of npd_sc_decode_mc in one launch: y is (n_snr, B, N) -- the received words of

@@ -47,6 +47,7 @@ SIGNATURES = [
     ("npd_scl_decode_mc", c_int, [c_void_p, c_void_p, c_float, c_int, c_void_p, c_u64, c_u64, c_i64, c_void_p,
                                   c_void_p]),
     ("npd_list_prune_select", c_int, [c_void_p, c_int, c_int, c_void_p]),
+    ("npd_list_prune_select64", c_int, [c_void_p, c_int, c_int, c_void_p]),
     ("npd_ml_supported", c_int, [c_void_p, c_int]),
     ("npd_ml_decode", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
     ("npd_map_decode", c_int, [c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_i64, c_void_p]),

@@ -166,5 +166,15 @@ NPD_HD inline unsigned prune_mask(const float* negm, int n, int k) {
     return m;
 }
 
+// The same over up to 64 candidates (list sizes 9 .. 32: 2L <= 64 candidates), as a 64-bit mask.
+NPD_HD inline unsigned long long prune_mask64(const float* negm, int n, int k) {
+    Q q[64];
+    for (int c = 0; c < n; ++c) q[c] = Q{negm[c], c};
+    nth_element(q, k - 1, n);
+    unsigned long long m = 0;
+    for (int c = 0; c < k; ++c) m |= 1ull << q[c].i;
+    return m;
+}
+
 }  // namespace nth
 }  // namespace npd

@@ -8,9 +8,10 @@ namespace scl {
 static int run(const npd_code* code, Args& a, hipStream_t s) {
     const CodeParams& p = code->p;
     if (p.N < 8 || p.N > 256) return fail(NPD_ENOTSUP, "scl_decode: N must be 8..256");
-    if (a.L < 1 || a.L > 8) return fail(NPD_EINVAL, "scl_decode: list size must be 1..8");
+    if (a.L < 1 || a.L > 32) return fail(NPD_EINVAL, "scl_decode: list size must be 1..32");
     if ((((uintptr_t)a.y) & 15) != 0) return fail(NPD_EINVAL, "scl_decode: y must be 16-byte aligned");
     if (a.B == 0) return NPD_OK;
+    if (a.L > 8) return p.pac ? run_pac_wide(p, a, s) : run_wide(p, a, s);
     if (p.pac) return run_pac(p, a, s);
     return dispatch<false>(p, a, s);
 }
@@ -59,5 +60,12 @@ extern "C" int npd_list_prune_select(const float* neg_metrics, int n, int keep, 
     NPD_ARG(neg_metrics != nullptr && mask_out != nullptr, "npd_list_prune_select: NULL pointer");
     NPD_ARG(n >= 1 && n <= 16 && keep >= 1 && keep <= n, "npd_list_prune_select: need 1 <= keep <= n <= 16");
     *mask_out = nth::prune_mask(neg_metrics, n, keep);
+    return NPD_OK;
+}
+
+extern "C" int npd_list_prune_select64(const float* neg_metrics, int n, int keep, uint64_t* mask_out) {
+    NPD_ARG(neg_metrics != nullptr && mask_out != nullptr, "npd_list_prune_select64: NULL pointer");
+    NPD_ARG(n >= 1 && n <= 64 && keep >= 1 && keep <= n, "npd_list_prune_select64: need 1 <= keep <= n <= 64");
+    *mask_out = nth::prune_mask64(neg_metrics, n, keep);
     return NPD_OK;
 }

@@ -1,8 +1,9 @@
 // npd_scl.hpp -- SC-List decoding kernels (PolarCode.scl_decode, polar.py:793-876, use_CRC=False), shared by
-// npd_scl.hip (the Polar instantiations and the C ABI) and npd_scl_pac.hip (the PAC instantiations).
+// npd_scl.hip (the Polar instantiations and the C ABI), npd_scl_pac.hip (the PAC instantiations) and, for lists of
+// 9 .. 32 paths, npd_scl_wide.hip / npd_scl_pac_wide.hip (G = 16 and 32, on the iterative LDS kernel at every N).
 //
 // Layout: a list of L paths per codeword lives in G = pow2ceil(L) adjacent lanes, one path per lane,
-// so 64/G codewords share a wave.  Every lane runs the same compile-time-unrolled min-sum SC schedule
+// so 64/G codewords share a wave.  At N <= 64 and L <= 8 every lane runs the same compile-time-unrolled min-sum SC schedule
 // as npd_sc_fast.hip on its own path state (LLRs of each level and partial sums in VGPRs); the
 // channel LLRs are identical for the whole group and never move.
 //
@@ -564,10 +565,19 @@ static int launch_n(const CodeParams& p, const Args& a, hipStream_t s) {
 // (L1/L2) and the path's own partial-sum bits at the four steps that read it (leaves 0, N/4, N/2, 3N/4): 158
 // rows = 40 KB of LDS per wave instead of 73 KB, so four waves (one per SIMD) fit a CU instead of two; a path
 // switch then never copies that level either.
+// Lists of 9 .. 32 paths (G = 16 or 32 lanes per codeword, 4 or 2 codewords per wave) run on this iterative form at
+// every N, 8 .. 64 included: a tree unrolled over 64 leaves with a 32-wide selection at each would be several times
+// the instruction cache, and here the selection exists once.  What is wider than at G <= 8:
+//   the live list size is min(2^min(slot, 5), L), the final one min(2^K, L);
+//   the survivor mask has 2s <= 64 bits (one ballot holds it) and list slot j finds its candidate, the j-th set
+//   bit, by a popcount bisection (nth_bit64) instead of j clear-lowest-bit steps;
+//   rank counting reads the group's 2G candidate metrics from two LDS rows that every lane parks its own pair in
+//   (G/2 broadcast 16-byte reads per lane) instead of 2G ds_bpermute;
+//   the exact tie rule (rare, out of line) reads the same two rows and keeps its 64 (value, index) pairs in scratch.
 template <int N>
 struct LdsRows {
     static constexpr int n = log2c<N>();
-    static constexpr int W = N / 32;
+    static constexpr int W = N >= 32 ? N / 32 : 1;
     static constexpr bool kTopRec = N >= 256;
     static constexpr int kLv = kTopRec ? N / 2 - 2 : N - 2;  // LLR rows (levels 1 .. n-1, or 1 .. n-2)
     static constexpr int kBS = kLv;          // beta sign words
@@ -575,7 +585,77 @@ struct LdsRows {
     static constexpr int kDS = kLv + 2 * W;  // decision sign words
     static constexpr int kDZ = kLv + 3 * W;  // decision zero words
     static constexpr int kRows = kLv + 4 * W;
+    static constexpr int kPark = kRows;      // G >= 16 only: keep metrics | flip metrics, one dword per lane each
+    static constexpr int kRowsWide = kRows + 2;
 };
+
+// position of the k-th set bit of m (k = 0 is the lowest), or 64 when m has at most k bits set
+__device__ __forceinline__ int nth_bit64(uint64_t m, int k) {
+    if (k >= __builtin_popcountll(m)) return 64;
+    int pos = 0;
+#pragma unroll
+    for (int w = 32; w >= 1; w >>= 1) {
+        const int cnt = __builtin_popcountll((m >> pos) & ((1ull << w) - 1ull));
+        if (k >= cnt) {
+            k -= cnt;
+            pos += w;
+        }
+    }
+    return pos;
+}
+
+// exact_mask for up to 32 paths: the group's metrics are read from the parked rows (PK[lane] keep, PK[64 + lane]
+// flip), so nothing is handed over in registers and the common path stores nothing for it
+__device__ __noinline__ uint64_t exact_mask64(const float* PK, int bl, int s, int L) {
+    float v[64];
+    for (int c2 = 0; c2 < s; ++c2) {
+        v[c2] = -1.0f * PK[bl + c2];
+        v[s + c2] = -1.0f * PK[kWave + bl + c2];
+    }
+    return nth::prune_mask64(v, 2 * s, L);
+}
+
+// list_select for G = 16 / 32: the survivors over [keep_0 .. keep_{s-1}, flip_0 .. flip_{s-1}] as a 64-bit mask
+template <int G>
+__device__ __forceinline__ uint64_t list_select_wide(float* PK, float m, float a, int j, int bl, int lane, int s,
+                                                     int L) {
+    static_assert(G == 16 || G == 32, "wide lists take 16 or 32 lanes");
+    if (2 * s <= L) return (1ull << (2 * s)) - 1ull;  // 2s <= 32
+    const float vk = m, vf = m + a;
+    int ltk = 0, lek = 0, ltf = 0, lef = 0;
+    PK[lane] = vk;
+    PK[kWave + lane] = vf;
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int q = 0; q < G / 4; ++q) {
+        if (4 * q < s) {  // wave-uniform
+            const f4 k4 = *reinterpret_cast<const f4*>(PK + bl + 4 * q);
+            const f4 f4v = *reinterpret_cast<const f4*>(PK + kWave + bl + 4 * q);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                if (4 * q + e < s) {
+                    ltk += (k4[e] < vk) + (f4v[e] < vk);
+                    lek += (k4[e] <= vk) + (f4v[e] <= vk);
+                    ltf += (k4[e] < vf) + (f4v[e] < vf);
+                    lef += (k4[e] <= vf) + (f4v[e] <= vf);
+                }
+            }
+        }
+    }
+    const bool act = j < s;
+    const bool sk = act && ltk < L;
+    const bool sf = act && ltf < L;
+    const bool st = act && ((ltk < L && lek > L) || (ltf < L && lef > L));
+    const unsigned long long bk = __ballot(sk), bf = __ballot(sf), bs = __ballot(st);
+    const uint64_t lowm = (1ull << s) - 1ull;  // s <= 32
+    uint64_t msel = ((bk >> bl) & lowm) | (((bf >> bl) & lowm) << s);
+    if (bs) {
+        const bool mine = ((bs >> bl) & ((1ull << G) - 1ull)) != 0ull;
+        if (mine) msel = exact_mask64(PK, bl, s, L);
+        __builtin_amdgcn_wave_barrier();
+    }
+    return msel;
+}
 
 __device__ __forceinline__ float beta_val(uint32_t sw, uint32_t zw, int b) {
     return bitsf((((sw >> b) & 1u) << 31) | (((zw >> b) & 1u) ? 0u : 0x3f800000u));
@@ -619,7 +699,7 @@ __global__ __launch_bounds__(64) void scl_lds_kernel(const CodeParams p, const A
     const int j = lane & (G - 1);
     const int base = lane - j;
     const int r = lane / G;
-    const int s_final = K >= 3 ? L : ((1 << K) < L ? (1 << K) : L);
+    const int s_final = K >= (G > 8 ? 5 : 3) ? L : ((1 << K) < L ? (1 << K) : L);
 
     uint32_t err_bits = 0, err_blocks = 0;
     for (int64_t t = blockIdx.x; t < a.ntiles; t += gridDim.x) {
@@ -727,9 +807,31 @@ __global__ __launch_bounds__(64) void scl_lds_kernel(const CodeParams p, const A
                 }
             } else {
                 const float av = __builtin_fabsf(l);
-                const int s = slot >= 3u ? L : ((1 << slot) < L ? (1 << slot) : L);
+                const int s = slot >= (G > 8 ? 5u : 3u) ? L : ((1 << slot) < L ? (1 << slot) : L);
                 float u;
-                if constexpr (G == 1) {
+                if constexpr (G > 8) {
+                    const uint64_t msel = list_select_wide<G>(LV + R::kPark * kWave, m, av, j, base, lane, s, L);
+                    // list slot j takes the j-th surviving candidate (list order); a slot past the last keeps itself
+                    const int cidx = nth_bit64(msel, j);
+                    const bool flip = cidx < 64 && cidx >= s;
+                    const int srcj = flip ? cidx - s : (cidx < 64 ? cidx : j);
+                    const int src = base + srcj;
+                    const float ls = __shfl(l, src, 64);
+                    const float ms = __shfl(m, src, 64);
+                    if constexpr (PAC) st = (uint32_t)__shfl((int)st, src, 64);
+                    if (src != lane) {
+                        for (int D = 1; D < (R::kTopRec ? n - 1 : n); ++D) {
+                            if ((i >> (D - 1)) & 1) continue;
+                            const int b0 = (1 << D) - 2;
+                            for (int e = 0; e < (1 << D); ++e) LV[(b0 + e) * kWave + lane] = LV[(b0 + e) * kWave + src];
+                        }
+#pragma unroll
+                        for (int w = 0; w < 4 * W; ++w) BW[(R::kBS + w) * kWave + lane] = BW[(R::kBS + w) * kWave + src];
+                    }
+                    u = sgn_bits(ls);
+                    if (flip) u = -u;
+                    m = flip ? ms + __builtin_fabsf(ls) : ms;
+                } else if constexpr (G == 1) {
                     u = sgn_bits(l);  // L = 1: plain SC with the metric tracked (pruning keeps the smaller one)
                     const uint32_t msel = list_select<G>(m, av, j, base, s, L);
                     if (!(msel & 1u)) {
@@ -909,7 +1011,7 @@ __global__ __launch_bounds__(64) void scl_lds_kernel(const CodeParams p, const A
 template <int N, int G, bool PAC>
 static int launch_lds(const CodeParams& p, Args a, hipStream_t s) {
     constexpr int T = 64 / G;
-    const size_t lds = (size_t)LdsRows<N>::kRows * kWave * sizeof(float);
+    const size_t lds = (size_t)(G > 8 ? LdsRows<N>::kRowsWide : LdsRows<N>::kRows) * kWave * sizeof(float);
     a.ntiles = (a.B + T - 1) / T;
     auto kern = scl_lds_kernel<N, G, PAC>;
     static bool attr_set = false;  // benign race (idempotent)
@@ -935,7 +1037,7 @@ static int launch_lds_n(const CodeParams& p, const Args& a, hipStream_t s) {
     return launch_lds<N, 8, PAC>(p, a, s);
 }
 
-// the kernel for p.N (8 .. 256, checked by the caller) and a.L (1 .. 8)
+// the kernel for p.N (8 .. 256, checked by the caller) and a.L (1 .. 8; larger lists go to dispatch_wide)
 template <bool PAC>
 static int dispatch(const CodeParams& p, const Args& a, hipStream_t s) {
     switch (p.N) {
@@ -948,8 +1050,30 @@ static int dispatch(const CodeParams& p, const Args& a, hipStream_t s) {
     }
 }
 
+// the kernel for p.N (8 .. 256) and a.L (9 .. 32): G = 16 up to 16 paths, G = 32 above
+template <int N, bool PAC>
+static int launch_wide_n(const CodeParams& p, const Args& a, hipStream_t s) {
+    if (a.L <= 16) return launch_lds<N, 16, PAC>(p, a, s);
+    return launch_lds<N, 32, PAC>(p, a, s);
+}
+
+template <bool PAC>
+static int dispatch_wide(const CodeParams& p, const Args& a, hipStream_t s) {
+    switch (p.N) {
+        case 8: return launch_wide_n<8, PAC>(p, a, s);
+        case 16: return launch_wide_n<16, PAC>(p, a, s);
+        case 32: return launch_wide_n<32, PAC>(p, a, s);
+        case 64: return launch_wide_n<64, PAC>(p, a, s);
+        case 128: return launch_wide_n<128, PAC>(p, a, s);
+        default: return launch_wide_n<256, PAC>(p, a, s);
+    }
+}
+
 // npd_scl_pac.hip: the PAC instantiations (arguments already checked by run())
 int run_pac(const CodeParams& p, const Args& a, hipStream_t s);
+// npd_scl_wide.hip / npd_scl_pac_wide.hip: list sizes 9 .. 32, Polar / PAC
+int run_wide(const CodeParams& p, const Args& a, hipStream_t s);
+int run_pac_wide(const CodeParams& p, const Args& a, hipStream_t s);
 
 }  // namespace scl
 }  // namespace npd

@@ -59,7 +59,7 @@ def save_standard(path: str, data: dict) -> None:
 
 def evaluate_standard(code, msg, rec, test_batch_size: int, list_size=None, gru=None, device=None):
     """test_standard (run_models.py:495-551) for the decoders of this package: SC always, SC-List when
-    ``list_size`` is given (polar.py:793), the CRISP GRU when ``gru=(net, RNN_decoder)``.  Returns
+    ``list_size`` (1 .. 32) is given (polar.py:793), the CRISP GRU when ``gru=(net, RNN_decoder)``.  Returns
     {decoder: {'ber': [...], 'bler': [...]}} over the SNRs of ``rec`` (dict order)."""
     from .utils import count_errors
     device = torch.device(device or "cuda")

@@ -137,7 +137,7 @@ class SCMonteCarlo(MonteCarlo):
 class SCLMonteCarlo(SCMonteCarlo):
     """SC-List decoding of a PolarCode (polar.py:793-876, run_models.py:327-331) or a PAC (the same list decoder
     with pac_sc_decode's leaf step, PAC.pac_scl_decode): generate + npd_scl_decode_mc (decode and count in one
-    launch; for PAC the counts compare v_hat[:, B] with the message)."""
+    launch; for PAC the counts compare v_hat[:, B] with the message).  list_size = 1 .. 32."""
 
     def __init__(self, code, list_size, snrs, total_cw, batch, seed=1234, rank=None, world=None, device=None):
         super().__init__(code, snrs, total_cw, batch, seed, rank, world, device, fused=False)
@@ -331,7 +331,7 @@ def _parse_args(argv=None):
     ap.add_argument("--test_size", type=int, default=1 << 20)
     ap.add_argument("--batch_size", type=int, default=1 << 20)
     ap.add_argument("--seed", type=int, default=1234)
-    ap.add_argument("--list_size", type=int, default=None, help="also run SC-List with this list size, 1 .. 8 (Polar and PAC)")
+    ap.add_argument("--list_size", type=int, default=None, help="also run SC-List with this list size, 1 .. 32 (Polar and PAC)")
     ap.add_argument("--lse", action="store_true", help="also run the exact-LSE sc_decode (Polar, polar.py:209)")
     ap.add_argument("--hard_decision", action="store_true", help="exact-LSE SC with sign decisions (else tanh)")
     ap.add_argument("--ml", action="store_true", help="also run maximum-likelihood decoding over the codebook "

@@ -133,7 +133,7 @@ class PAC:
 
     # ------------------------------------------------------------------ SC-List
     def pac_scl_decode(self, corrupted_codewords, snr, L=1, want_llrs=True):
-        """SC-List decoding of the PAC code; returns (leaf LLRs of the chosen path (B,N), v_hat[:, B] (B,K),
+        """SC-List decoding of the PAC code with L = 1 .. 32 paths; returns (leaf LLRs of the chosen path (B,N), v_hat[:, B] (B,K),
         u_hat (B,N)), the shape of pac_sc_decode's return.
 
         The reference has no PAC list decoder: this is PolarCode.scl_decode (polar.py:793-876, use_CRC=False)

@@ -172,7 +172,7 @@ class PolarCode:
 
     # ------------------------------------------------------------------ SC-List (polar.py:793-876)
     def scl_decode(self, corrupted_codewords, snr, L=1, use_CRC=False, want_llrs=True):
-        """SC-List decoding; returns (leaf LLRs of the chosen path (B,N), msg_hat (B,K)).
+        """SC-List decoding with L = 1 .. 32 paths; returns (leaf LLRs of the chosen path (B,N), msg_hat (B,K)).
 
         The chosen path's leaf LLRs are recomputed by a genie SC pass with its decisions (identical
         values); ``want_llrs=False`` skips that pass and returns None in their place."""
@@ -194,6 +194,8 @@ class PolarCode:
         return _lib.home(leaf, corrupted_codewords), _lib.home(hat, corrupted_codewords)
 
     def scl_decode_mc(self, y, snr, L, seed, cw_offset, counters, msg_hat=None):
+        """counters += {bit errors, block errors} of scl_decode (L = 1 .. 32) against the Philox messages of codewords
+        cw_offset .. cw_offset + batch - 1, decoded and counted in one launch."""
         _lib.require_gpu(y, "y")
         if y.dim() != 2 or y.shape[1] != self.N:
             raise ValueError(f"y must be (batch, {self.N}), got {tuple(y.shape)}")
