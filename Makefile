@@ -24,6 +24,10 @@ EXTRA_npd_scl := -fno-honor-nans
 EXTRA_npd_scl_pac := -fno-honor-nans
 EXTRA_npd_scl_wide := -fno-honor-nans
 EXTRA_npd_scl_pac_wide := -fno-honor-nans
+EXTRA_npd_scl_crc := -fno-honor-nans
+EXTRA_npd_scl_crc_pac := -fno-honor-nans
+EXTRA_npd_scl_crc_wide := -fno-honor-nans
+EXTRA_npd_scl_crc_pac_wide := -fno-honor-nans
 # the ML/MAP epilogues read every MFMA result on the VALU: keep the accumulators in VGPRs (no v_accvgpr_read per value)
 EXTRA_npd_ml := -mllvm -amdgpu-mfma-vgpr-form=1
 

@@ -183,6 +183,56 @@ int npd_list_prune_select(const float* neg_metrics, int n, int keep, uint32_t* m
 /* The same for 1 <= keep <= n <= 64 candidates (list sizes 9 .. 32 prune up to 64), as a 64-bit mask. */
 int npd_list_prune_select64(const float* neg_metrics, int n, int keep, uint64_t* mask_out);
 
+/* ---------------------------------------------------------------------------------- CRC-aided SC-List decode */
+/*
+ * PolarCode.scl_decode(y, snr, L, use_CRC=True) (polar.py:849-866) with get_CRC / CRC_check / encode_with_crc
+ * (polar.py:738-775).  The reference's helpers do not run as written (they read a module global that exists only when
+ * polar.py is the script) and, once they do, attach the CRC with the opposite bit convention to the one CRC_check
+ * reads, so a correctly received word never passes.  This project therefore defines the decoder, taking from the
+ * reference what is well defined: the polynomial division (polar.py:738-748), its three polynomials and the selection
+ * rule (polar.py:860-866).  Polar and PAC codes.
+ *
+ * Polynomial.  crc_poly: bit i is the coefficient of x^i; the degree c is the index of the top set bit.  Rules:
+ *   1 <= c <= 24, bit 0 set, c < K; anything else returns NPD_EINVAL.  The reference's polynomials are 0xB (c = 3),
+ *   0x1D5 (c = 8) and 0x11021 (c = 16).
+ * Bits.  Symbol -1 is bit 1 and +1 is bit 0, the convention of the Philox messages (msg = 1 - 2 bit).  A decision of 0
+ *   is neither.
+ * CRC.  The K information slots, in the order of the sorted information set (the column order of msg), carry
+ *   m_0 .. m_{K-c-1} and then r_0 .. r_{c-1}, where r(x) = (sum_k m_k x^(K-c-1-k)) x^c mod g(x) and r_i is the
+ *   coefficient of x^(c-1-i): the plain division, MSB first, zero initial register, no reflection, no final XOR.  For
+ *   PAC codes the CRC covers the message before the convolution (pac_encode([msg, crc])).
+ * A path passes if its K information decisions (Polar: u_hat at the information set; PAC: v_hat there) contain no 0
+ *   and, read as a polynomial of degree K - 1, leave remainder 0.
+ * Selection (polar.py:860-866).  Over the live list of min(2^K, list_size) paths in list order: the passing path of
+ *   smallest path metric, the first in list order on a tie; if no path passes, the path of smallest metric, the first
+ *   in list order on a tie; crc_ok = 1 or 0 accordingly.  Nothing else about the list changes: forking, metrics,
+ *   pruning and tie rules are those of npd_scl_decode; the distance step is not run.  (The tie rules are those of the
+ *   (value, index) reduction that npd_scl_decode's final step uses; no word set tried produced two passing paths tied
+ *   at the minimum, so no test exercises that one.)
+ *
+ * npd_crc_attach: out (B,K) = [msg (B,K-c) unchanged | the CRC columns as +-1, computed from bit = msg < 0].
+ * npd_mc_generate_crc: npd_mc_generate whose message bits 0 .. K-c-1 are the Philox message stream and whose bits
+ *   K-c .. K-1 are their CRC; the first K-c message columns and the noise are exactly those npd_mc_generate gives.
+ *   msg (B,K) and x optional, y required.
+ * npd_scl_decode_crc: limits of npd_scl_decode (Polar and PAC handles, 8 <= N <= 256, 1 <= list_size <= 32, y 16-byte
+ *   aligned).  Outputs of the chosen path, each optional but at least one: msg_hat (B,K) (the CRC columns included),
+ *   u_hat (B,N), crc_ok (B) int32.  The chosen path's leaf LLRs are npd_sc_decode(..., gt = u_hat), as for
+ *   npd_scl_decode.
+ * npd_scl_decode_crc_mc: decode and count in one launch; counters[0..2] (device uint64, not reset) += {bit errors over
+ *   the K-c message bits against the Philox message (a 0 counts as an error), block errors over the same K-c bits,
+ *   words with crc_ok == 0}.
+ * All four check every pointer and the polynomial before any HIP call, are stream-ordered, allocate nothing, and
+ * return NPD_OK for B = 0.
+ */
+int npd_crc_attach(const float* msg, float* out, int64_t B, int K, uint32_t crc_poly, void* stream);
+int npd_mc_generate_crc(const npd_code* code, uint32_t crc_poly, float* msg, float* x, float* y, int64_t B, float sigma,
+                        uint64_t seed, uint32_t snr_index, uint64_t cw_offset, void* stream);
+int npd_scl_decode_crc(const npd_code* code, const float* y, float llr_scale, int list_size, uint32_t crc_poly,
+                       float* msg_hat, float* u_hat, int32_t* crc_ok, int64_t B, void* stream);
+int npd_scl_decode_crc_mc(const npd_code* code, const float* y, float llr_scale, int list_size, uint32_t crc_poly,
+                          float* msg_hat, uint64_t seed, uint64_t cw_offset, int64_t B, unsigned long long* counters,
+                          void* stream);
+
 /*
  * A whole SNR sweep of npd_sc_decode_mc in one launch: y is (n_snr, B, N) -- the received words of
  * the same codewords cw_offset .. cw_offset+B-1 at n_snr SNR points (the reference's per-SNR loop,

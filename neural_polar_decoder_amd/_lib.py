@@ -46,6 +46,13 @@ SIGNATURES = [
     ("npd_scl_decode", c_int, [c_void_p, c_void_p, c_float, c_int, c_void_p, c_void_p, c_i64, c_void_p]),
     ("npd_scl_decode_mc", c_int, [c_void_p, c_void_p, c_float, c_int, c_void_p, c_u64, c_u64, c_i64, c_void_p,
                                   c_void_p]),
+    ("npd_crc_attach", c_int, [c_void_p, c_void_p, c_i64, c_int, c_u32, c_void_p]),
+    ("npd_mc_generate_crc", c_int, [c_void_p, c_u32, c_void_p, c_void_p, c_void_p, c_i64, c_float, c_u64, c_u32, c_u64,
+                                    c_void_p]),
+    ("npd_scl_decode_crc", c_int, [c_void_p, c_void_p, c_float, c_int, c_u32, c_void_p, c_void_p, c_void_p, c_i64,
+                                   c_void_p]),
+    ("npd_scl_decode_crc_mc", c_int, [c_void_p, c_void_p, c_float, c_int, c_u32, c_void_p, c_u64, c_u64, c_i64, c_void_p,
+                                      c_void_p]),
     ("npd_list_prune_select", c_int, [c_void_p, c_int, c_int, c_void_p]),
     ("npd_list_prune_select64", c_int, [c_void_p, c_int, c_int, c_void_p]),
     ("npd_ml_supported", c_int, [c_void_p, c_int]),

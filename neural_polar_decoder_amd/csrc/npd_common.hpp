@@ -131,4 +131,14 @@ inline int grid_for(int64_t tiles, int per_cu_blocks, int num_cu) {
 
 int device_cu_count();
 
+// degree c of a CRC polynomial (bit i = coefficient of x^i) for a code of K information bits, or -1 if it breaks a
+// rule of include/npd.h: 1 <= c <= 24, bit 0 set, c < K
+inline int crc_degree(uint32_t poly, int K) {
+    int c = -1;
+    for (int i = 0; i < 32; ++i)
+        if ((poly >> i) & 1u) c = i;
+    if (c < 1 || c > 24 || !(poly & 1u) || c >= K) return -1;
+    return c;
+}
+
 }  // namespace npd

@@ -88,11 +88,13 @@ __global__ __launch_bounds__(256) void awgn_kernel(const float4* __restrict__ x,
 // Plotkin butterfly as XOR on 32-bit words; the codeword's bits go to LDS.  Phase 2, one lane per 16-B
 // chunk of the wave's 64 x N output tile: BPSK + sigma * N(0,1) (Philox counter = (chunk, codeword), so
 // the mapping of work to lanes does not change any value), stored coalesced.
-template <int N>
+// CRC (npd_mc_generate_crc; the CRC = false instantiations compile to what they were): message bits K-c .. K-1 are
+// replaced, in the bit domain, by the CRC of the Philox bits 0 .. K-c-1 (include/npd.h) before anything reads them.
+template <int N, bool CRC = false>
 __global__ __launch_bounds__(256) void mc_generate_kernel(const CodeParams p, float* __restrict__ msg,
                                                           float* __restrict__ x, float* __restrict__ y, int64_t B,
                                                           float sigma, uint64_t seed, uint32_t snr_index,
-                                                          uint64_t cw_offset) {
+                                                          uint64_t cw_offset, uint32_t crc_poly, int crc_c) {
     constexpr int NW = (N + 31) / 32;
     constexpr int MB = (N + 127) / 128;  // Philox blocks for up to N message bits
     constexpr int C = N / 4;             // 16-B chunks per row
@@ -108,6 +110,29 @@ __global__ __launch_bounds__(256) void mc_generate_kernel(const CodeParams p, fl
         for (int blk = 0; blk < MB; ++blk) {
             const u32x4 o = philox_block(seed, kStreamMsg, cw, (uint32_t)blk);
             m[4 * blk + 0] = o.x; m[4 * blk + 1] = o.y; m[4 * blk + 2] = o.z; m[4 * blk + 3] = o.w;
+        }
+        if constexpr (CRC) {
+            const int kc = p.K - crc_c;
+            uint32_t reg = 0u;
+#pragma unroll
+            for (int q = 0; q < 4 * MB; ++q) {
+                const int nb = kc - 32 * q < 32 ? kc - 32 * q : 32;
+                for (int bb = 0; bb < nb; ++bb) {
+                    reg = (reg << 1) | ((m[q] >> bb) & 1u);
+                    reg ^= crc_poly & (0u - ((reg >> crc_c) & 1u));
+                }
+            }
+            for (int z = 0; z < crc_c; ++z) {  // m(x) x^c
+                reg <<= 1;
+                reg ^= crc_poly & (0u - ((reg >> crc_c) & 1u));
+            }
+            for (int i = 0; i < crc_c; ++i) {  // r_i, the coefficient of x^(c-1-i), is message bit K-c+i
+                const int k = kc + i;
+                const uint32_t msk = 1u << (k & 31);
+                const uint32_t bit = ((reg >> (crc_c - 1 - i)) & 1u) ? msk : 0u;
+#pragma unroll
+                for (int q = 0; q < 4 * MB; ++q) m[q] = ((k >> 5) == q) ? ((m[q] & ~msk) | bit) : m[q];
+            }
         }
         if (msg) {
 #pragma unroll
@@ -195,6 +220,30 @@ __global__ __launch_bounds__(256) void mc_generate_kernel(const CodeParams p, fl
             yt[g] = yv;
             if (xt) xt[g] = make_float4(xv[0], xv[1], xv[2], xv[3]);
         }
+    }
+}
+
+// ---------------------------------------------------------------------------------- CRC attach
+// out (B, K) = [msg (B, K - c) unchanged | CRC of bit = msg < 0 as +-1], one thread per row (rows are short and the
+// division is serial; the Monte-Carlo path computes its CRC inside mc_generate_kernel instead)
+__global__ __launch_bounds__(256) void crc_attach_kernel(const float* __restrict__ msg, float* __restrict__ out,
+                                                         int64_t B, int K, int c, uint32_t poly) {
+    const int kc = K - c;
+    for (int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; b < B; b += (int64_t)gridDim.x * blockDim.x) {
+        const float* mr = msg + b * kc;
+        float* orow = out + b * K;
+        uint32_t reg = 0u;
+        for (int k = 0; k < kc; ++k) {
+            const float v = mr[k];
+            orow[k] = v;
+            reg = (reg << 1) | (v < 0.0f ? 1u : 0u);
+            reg ^= poly & (0u - ((reg >> c) & 1u));
+        }
+        for (int z = 0; z < c; ++z) {  // m(x) x^c
+            reg <<= 1;
+            reg ^= poly & (0u - ((reg >> c) & 1u));
+        }
+        for (int i = 0; i < c; ++i) orow[kc + i] = ((reg >> (c - 1 - i)) & 1u) ? -1.0f : 1.0f;
     }
 }
 
@@ -323,8 +372,17 @@ static int mc_gen_launch(const npd_code* code, float* msg, float* x, float* y, i
                          uint32_t snr_index, uint64_t cw_offset, hipStream_t s) {
     const int64_t blocks = (B + 4 * kWave - 1) / (4 * kWave);
     hipLaunchKernelGGL(gen::mc_generate_kernel<N>, dim3((unsigned)blocks), dim3(256), 0, s, code->p, msg, x, y, B, sigma,
-                       seed, snr_index, cw_offset);
+                       seed, snr_index, cw_offset, 0u, 0);
     return launch_check("mc_generate_kernel launch");
+}
+
+template <int N>
+static int mc_gen_crc_launch(const npd_code* code, uint32_t crc_poly, int c, float* msg, float* x, float* y, int64_t B,
+                             float sigma, uint64_t seed, uint32_t snr_index, uint64_t cw_offset, hipStream_t s) {
+    const int64_t blocks = (B + 4 * kWave - 1) / (4 * kWave);
+    hipLaunchKernelGGL((gen::mc_generate_kernel<N, true>), dim3((unsigned)blocks), dim3(256), 0, s, code->p, msg, x, y,
+                       B, sigma, seed, snr_index, cw_offset, crc_poly, c);
+    return launch_check("mc_generate_kernel (CRC) launch");
 }
 
 extern "C" int npd_mc_generate(const npd_code* code, float* msg, float* x, float* y, int64_t B, float sigma,
@@ -346,6 +404,42 @@ extern "C" int npd_mc_generate(const npd_code* code, float* msg, float* x, float
         case 256: return mc_gen_launch<256>(code, msg, x, y, B, sigma, seed, snr_index, cw_offset, s);
         default: return fail(NPD_EINVAL, "npd_mc_generate: unsupported N");
     }
+}
+
+extern "C" int npd_mc_generate_crc(const npd_code* code, uint32_t crc_poly, float* msg, float* x, float* y, int64_t B,
+                                   float sigma, uint64_t seed, uint32_t snr_index, uint64_t cw_offset, void* stream) {
+    NPD_ARG(code != nullptr, "npd_mc_generate_crc: code is NULL");
+    NPD_ARG(B >= 0, "npd_mc_generate_crc: B < 0");
+    const int c = crc_degree(crc_poly, code->p.K);
+    NPD_ARG(c > 0, "npd_mc_generate_crc: crc_poly needs degree 1 .. 24 below K and bit 0 set");
+    if (B == 0) return NPD_OK;
+    NPD_ARG(y != nullptr, "npd_mc_generate_crc: y is NULL");
+    NPD_ARG(((uintptr_t)y & 15) == 0 && ((uintptr_t)x & 15) == 0, "npd_mc_generate_crc: x and y must be 16-byte aligned");
+    NPD_ARG(B <= (int64_t)0x7fffffff * 256, "npd_mc_generate_crc: B too large for one call");
+    hipStream_t s = (hipStream_t)stream;
+    switch (code->p.N) {
+        case 4: return mc_gen_crc_launch<4>(code, crc_poly, c, msg, x, y, B, sigma, seed, snr_index, cw_offset, s);
+        case 8: return mc_gen_crc_launch<8>(code, crc_poly, c, msg, x, y, B, sigma, seed, snr_index, cw_offset, s);
+        case 16: return mc_gen_crc_launch<16>(code, crc_poly, c, msg, x, y, B, sigma, seed, snr_index, cw_offset, s);
+        case 32: return mc_gen_crc_launch<32>(code, crc_poly, c, msg, x, y, B, sigma, seed, snr_index, cw_offset, s);
+        case 64: return mc_gen_crc_launch<64>(code, crc_poly, c, msg, x, y, B, sigma, seed, snr_index, cw_offset, s);
+        case 128: return mc_gen_crc_launch<128>(code, crc_poly, c, msg, x, y, B, sigma, seed, snr_index, cw_offset, s);
+        case 256: return mc_gen_crc_launch<256>(code, crc_poly, c, msg, x, y, B, sigma, seed, snr_index, cw_offset, s);
+        default: return fail(NPD_EINVAL, "npd_mc_generate_crc: unsupported N");
+    }
+}
+
+extern "C" int npd_crc_attach(const float* msg, float* out, int64_t B, int K, uint32_t crc_poly, void* stream) {
+    NPD_ARG(B >= 0, "npd_crc_attach: B < 0");
+    NPD_ARG(K >= 2 && K <= kMaxN, "npd_crc_attach: K must be 2 .. 256");
+    const int c = crc_degree(crc_poly, K);
+    NPD_ARG(c > 0, "npd_crc_attach: crc_poly needs degree 1 .. 24 below K and bit 0 set");
+    NPD_ARG(B == 0 || (msg != nullptr && out != nullptr), "npd_crc_attach: null pointer");
+    if (B == 0) return NPD_OK;
+    const int grid = grid_for((B + 255) / 256, 8, device_cu_count());
+    hipLaunchKernelGGL(gen::crc_attach_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, msg, out, B, K, c,
+                       crc_poly);
+    return launch_check("crc_attach_kernel launch");
 }
 
 static int count_launch(gen::CountArgs& a, hipStream_t s) {

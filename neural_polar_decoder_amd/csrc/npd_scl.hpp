@@ -1,6 +1,8 @@
 // npd_scl.hpp -- SC-List decoding kernels (PolarCode.scl_decode, polar.py:793-876, use_CRC=False), shared by
 // npd_scl.hip (the Polar instantiations and the C ABI), npd_scl_pac.hip (the PAC instantiations) and, for lists of
 // 9 .. 32 paths, npd_scl_wide.hip / npd_scl_pac_wide.hip (G = 16 and 32, on the iterative LDS kernel at every N).
+// The CRC-aided selection (use_CRC=True, polar.py:849-866; template flag CRC, see "CRC-aided selection" below) is a
+// second epilogue of the same kernels, instantiated in npd_scl_crc.hip / _pac / _wide / _pac_wide.
 //
 // Layout: a list of L paths per codeword lives in G = pow2ceil(L) adjacent lanes, one path per lane,
 // so 64/G codewords share a wave.  At N <= 64 and L <= 8 every lane runs the same compile-time-unrolled min-sum SC schedule
@@ -42,7 +44,7 @@ struct Args {
     const float* y;
     float* msg;                    // (B,K) or null
     float* uhat;                   // (B,N) or null
-    unsigned long long* counters;  // {bit errors, block errors} or null
+    unsigned long long* counters;  // {bit errors, block errors} (CRC: and {words no path passed for}) or null
     uint64_t seed;
     uint64_t cw_offset;
     int64_t B;
@@ -50,6 +52,9 @@ struct Args {
     float scale;
     int L;
     uint32_t count;
+    uint32_t crc_poly;             // CRC: the polynomial (bit i = coefficient of x^i) and its degree
+    int crc_c;
+    int32_t* crc_ok;               // CRC: (B) or null
 };
 
 typedef float f4 __attribute__((ext_vector_type(4)));
@@ -152,6 +157,90 @@ __device__ __forceinline__ uint64_t pac_unconv_fast(uint64_t x, uint32_t tap) {
         x = acc;
     }
     return x;
+}
+
+// ---------------------------------------------------------------------------------- CRC-aided selection
+// Template flag CRC (npd_scl_decode_crc, instantiated in npd_scl_crc*.hip; the CRC = false instantiations compile to
+// what they were): the distance step is replaced by a CRC over every surviving path's K information decisions
+// (Polar: u_hat, PAC: v_hat, so every live lane runs the inverse convolution, not only the winner).  The
+// information positions of a word are the set bits of ~frozen[w], a wave-uniform mask: the division needs no
+// info[] loads and no per-bit LDS reads.  The register is c bits wide plus the bit shifted out: polar.py:738-748's
+// division, MSB first, zero initial value, no reflection, no final XOR.
+
+// information positions among the NB positions that word w holds (wave-uniform)
+template <int NB>
+__device__ __forceinline__ uint32_t info_word(const CodeParams& p, int w) {
+    uint32_t iw = ~p.frozen[w];
+    if constexpr (NB < 32) iw &= (1u << NB) - 1u;
+    return iw;
+}
+
+// remainder of the path's information bits (sign words vs, bit 1 = symbol -1) read as a polynomial of degree K - 1
+template <int W, int NB>
+__device__ __forceinline__ uint32_t crc_divide(const uint32_t (&vs)[W], const CodeParams& p, uint32_t poly, int c) {
+    uint32_t reg = 0u;
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+        const uint32_t word = vs[w];
+        for (uint32_t im = info_word<NB>(p, w); im != 0u; im &= im - 1u) {
+            reg = (reg << 1) | ((word >> __builtin_ctz(im)) & 1u);
+            reg ^= poly & (0u - ((reg >> c) & 1u));
+        }
+    }
+    return reg;
+}
+
+// The list slot chosen for one group of G lanes: the passing path of smallest metric, or, when no path of the group
+// passes (decided from a ballot of the pass flags, not from the key), the live path of smallest metric; the
+// (value, index) butterfly of the ML step, so the first in list order wins a tie.
+template <int G>
+__device__ __forceinline__ int crc_choose(float m, bool pass, bool live, int j, int base, bool& any) {
+    const unsigned long long bal = __ballot(pass);
+    const unsigned long long gm = G >= 64 ? ~0ull : ((1ull << G) - 1ull);
+    any = ((bal >> base) & gm) != 0ull;
+    float bd = (any ? pass : live) ? m : __builtin_inff();
+    int bi = j;
+#pragma unroll
+    for (int off = 1; off < G; off <<= 1) {
+        const float od = __shfl_xor(bd, off, 64);
+        const int oi = __shfl_xor(bi, off, 64);
+        if (od < bd || (od == bd && oi < bi)) {
+            bd = od;
+            bi = oi;
+        }
+    }
+    return bi;
+}
+
+// word q of the Philox message words (a select chain: no dynamically indexed register array)
+template <int MW>
+__device__ __forceinline__ uint32_t pick_word(const uint32_t (&mw)[MW], int q) {
+    uint32_t w = mw[0];
+#pragma unroll
+    for (int t = 1; t < MW; ++t) w = (q == t) ? mw[t] : w;
+    return w;
+}
+
+// The winner's lane: msg_hat row (K values, the CRC columns included) from the sign words vs and zero words zs at the
+// information positions in order, and the errors of the first kc = K - c of them against the Philox message words.
+template <int W, int NB, int MW>
+__device__ __forceinline__ uint32_t crc_emit(const uint32_t (&vs)[W], const uint32_t (&zs)[W], const CodeParams& p,
+                                             float* mrow, const uint32_t (&mw)[MW], int kc) {
+    uint32_t e = 0u, cur = 0u;
+    int k = 0;
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+        for (uint32_t im = info_word<NB>(p, w); im != 0u; im &= im - 1u) {
+            const int b = __builtin_ctz(im);
+            if ((k & 31) == 0) cur = pick_word<MW>(mw, k >> 5);
+            const uint32_t sb = (vs[w] >> b) & 1u, zb = (zs[w] >> b) & 1u;
+            if (mrow) mrow[k] = zb ? 0.0f : (sb ? -1.0f : 1.0f);
+            e += k < kc ? ((sb ^ (cur & 1u)) | zb) : 0u;
+            cur >>= 1;
+            ++k;
+        }
+    }
+    return e;
 }
 
 // first position whose partial sum is still read after leaf I: the start of the highest ancestor that
@@ -359,7 +448,7 @@ __device__ __forceinline__ void node(Lane<N, G>& c, int lane) {
     }
 }
 
-template <int N, int G, bool PAC>
+template <int N, int G, bool PAC, bool CRC = false>
 __global__ __launch_bounds__(64) void scl_kernel(const CodeParams p, const Args a) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     constexpr int n = log2c<N>();
@@ -380,6 +469,7 @@ __global__ __launch_bounds__(64) void scl_kernel(const CodeParams p, const Args 
     const int s_final = K >= 3 ? a.L : ((1 << K) < a.L ? (1 << K) : a.L);
 
     uint32_t err_bits = 0, err_blocks = 0;
+    [[maybe_unused]] uint32_t err_crc = 0;
     for (int64_t t = blockIdx.x; t < a.ntiles; t += gridDim.x) {
         const int64_t row0 = t * T;
         // ---- stage the tile's received words in LDS (coalesced), swizzled rows
@@ -415,6 +505,61 @@ __global__ __launch_bounds__(64) void scl_kernel(const CodeParams p, const Args 
             c.smk = p.smask;
         }
         node<PAC, N, G, n, 0>(c, lane);
+
+        if constexpr (CRC) {
+            // ---- CRC-aided choice (polar.py:860-866): every live lane divides its own information decisions
+            uint32_t vs[W], zs[W];
+            uint32_t zany = 0u;
+#pragma unroll
+            for (int w = 0; w < W; ++w) {
+                vs[w] = PAC ? 0u : c.sm[w];
+                zs[w] = c.zm[w];
+                zany |= c.zm[w];  // zero decisions arise at information leaves only
+            }
+            if constexpr (PAC) {
+                if (zany == 0u) {
+                    const uint64_t u64 = (uint64_t)c.sm[0] | (W > 1 ? (uint64_t)c.sm[W - 1] << 32 : 0ull);
+                    const uint64_t v64 = pac_unconv_fast<N>(u64, p.tapmask);
+                    vs[0] = (uint32_t)v64;
+                    if constexpr (W > 1) vs[W - 1] = (uint32_t)(v64 >> 32);
+                } else {
+                    uint32_t st = 0u;
+#pragma unroll
+                    for (int w = 0; w < W; ++w)
+                        vs[w] = pac_unconv_word(c.sm[w], c.zm[w], N < 32 ? N : 32, st, p.tapmask, p.smask);
+                }
+            }
+            const uint32_t reg = crc_divide<W, (N < 32 ? N : 32)>(vs, p, a.crc_poly, a.crc_c);
+            const bool live = c.j < s_final;
+            bool anyp;
+            const int bi = crc_choose<G>(c.m, live && reg == 0u && zany == 0u, live, c.j, c.base, anyp);
+            const int64_t cwc = row0 + r;
+            if (c.j == bi && cwc < a.B) {
+                uint32_t mw[4] = {0u, 0u, 0u, 0u};
+                if (a.count) {
+                    const u32x4 o = philox_block(a.seed, kStreamMsg, a.cw_offset + (uint64_t)cwc, 0u);
+                    mw[0] = o.x;
+                    mw[1] = o.y;
+                    mw[2] = o.z;
+                    mw[3] = o.w;
+                }
+                const uint32_t e = crc_emit<W, (N < 32 ? N : 32), 4>(vs, zs, p, a.msg ? a.msg + cwc * K : nullptr, mw,
+                                                                     K - a.crc_c);
+                if (a.uhat) {
+                    float* urow = a.uhat + cwc * N;
+#pragma unroll
+                    for (int k = 0; k < N; ++k) {
+                        const uint32_t sb = (c.sm[k >> 5] >> (k & 31)) & 1u, zb = (c.zm[k >> 5] >> (k & 31)) & 1u;
+                        urow[k] = zb ? 0.0f : (sb ? -1.0f : 1.0f);
+                    }
+                }
+                if (a.crc_ok) a.crc_ok[cwc] = anyp ? 1 : 0;
+                err_bits += e;
+                err_blocks += e ? 1u : 0u;
+                err_crc += anyp ? 0u : 1u;
+            }
+            continue;
+        }
 
         // ---- ML choice (polar.py:868-874): codeword of each path from its decision bits
         uint32_t S[W], Z[W];
@@ -519,15 +664,19 @@ __global__ __launch_bounds__(64) void scl_kernel(const CodeParams p, const Args 
             atomicAdd(a.counters + 0, (unsigned long long)eb);
             atomicAdd(a.counters + 1, (unsigned long long)bl);
         }
+        if constexpr (CRC) {
+            const uint32_t cf = wave_sum_u32(err_crc);
+            if (lane == 0) atomicAdd(a.counters + 2, (unsigned long long)cf);
+        }
     }
 }
 
-template <int N, int G, bool PAC>
+template <int N, int G, bool PAC, bool CRC = false>
 static int launch(const CodeParams& p, Args a, hipStream_t s) {
     constexpr int T = 64 / G;
     const size_t lds = (size_t)T * N * 4;
     a.ntiles = (a.B + T - 1) / T;
-    auto kern = scl_kernel<N, G, PAC>;
+    auto kern = scl_kernel<N, G, PAC, CRC>;
     int occ = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, 64, lds) != hipSuccess || occ <= 0) {
         (void)hipGetLastError();
@@ -538,12 +687,12 @@ static int launch(const CodeParams& p, Args a, hipStream_t s) {
     return launch_check("scl_kernel launch");
 }
 
-template <int N, bool PAC>
+template <int N, bool PAC, bool CRC = false>
 static int launch_n(const CodeParams& p, const Args& a, hipStream_t s) {
-    if (a.L == 1) return launch<N, 1, PAC>(p, a, s);
-    if (a.L == 2) return launch<N, 2, PAC>(p, a, s);
-    if (a.L <= 4) return launch<N, 4, PAC>(p, a, s);
-    return launch<N, 8, PAC>(p, a, s);
+    if (a.L == 1) return launch<N, 1, PAC, CRC>(p, a, s);
+    if (a.L == 2) return launch<N, 2, PAC, CRC>(p, a, s);
+    if (a.L <= 4) return launch<N, 4, PAC, CRC>(p, a, s);
+    return launch<N, 8, PAC, CRC>(p, a, s);
 }
 
 // ---------------------------------------------------------------------------------- N >= 128
@@ -682,7 +831,7 @@ __device__ __forceinline__ f4 top4(const f4* y4, float scale, int x, bool right,
 
 // PAC: the convolution state is one VGPR per lane (no LDS row: the N = 256 kernel keeps its 158 rows and its four
 // waves per CU); after the last leaf the beta sign rows are dead, and the chosen path writes v_hat's sign words there.
-template <int N, int G, bool PAC>
+template <int N, int G, bool PAC, bool CRC = false>
 __global__ __launch_bounds__(64) void scl_lds_kernel(const CodeParams p, const Args a) {
     extern __shared__ __attribute__((aligned(16))) char lds_raw[];
     using R = LdsRows<N>;
@@ -702,6 +851,7 @@ __global__ __launch_bounds__(64) void scl_lds_kernel(const CodeParams p, const A
     const int s_final = K >= (G > 8 ? 5 : 3) ? L : ((1 << K) < L ? (1 << K) : L);
 
     uint32_t err_bits = 0, err_blocks = 0;
+    [[maybe_unused]] uint32_t err_crc = 0;
     for (int64_t t = blockIdx.x; t < a.ntiles; t += gridDim.x) {
         const int64_t cw = t * T + r;
         const int64_t cwc = cw < a.B ? cw : a.B - 1;
@@ -901,6 +1051,58 @@ __global__ __launch_bounds__(64) void scl_lds_kernel(const CodeParams p, const A
             }
         }
 
+        if constexpr (CRC) {
+            // ---- CRC-aided choice (polar.py:860-866): every live lane divides its own information decisions
+            uint32_t us[W], vs[W], zs[W];
+            uint32_t zany = 0u;
+#pragma unroll
+            for (int w = 0; w < W; ++w) {
+                us[w] = BWL(R::kDS + w);
+                zs[w] = BWL(R::kDZ + w);
+                vs[w] = us[w];
+                zany |= zs[w];  // zero decisions arise at information leaves only
+            }
+            if constexpr (PAC) {
+                uint32_t cs = 0u;
+#pragma unroll
+                for (int w = 0; w < W; ++w) vs[w] = pac_unconv_word(us[w], zs[w], 32, cs, p.tapmask, p.smask);
+            }
+            const uint32_t reg = crc_divide<W, (N < 32 ? N : 32)>(vs, p, a.crc_poly, a.crc_c);
+            const bool live = j < s_final;
+            bool anyp;
+            const int bj = crc_choose<G>(m, live && reg == 0u && zany == 0u, live, j, base, anyp);
+            if (j == bj && cw < a.B) {
+                uint32_t mw[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+                if (a.count) {
+#pragma unroll
+                    for (int blk = 0; blk < 2; ++blk) {
+                        if (blk * 128 < K) {
+                            const u32x4 o = philox_block(a.seed, kStreamMsg, a.cw_offset + (uint64_t)cw, (uint32_t)blk);
+                            mw[4 * blk + 0] = o.x;
+                            mw[4 * blk + 1] = o.y;
+                            mw[4 * blk + 2] = o.z;
+                            mw[4 * blk + 3] = o.w;
+                        }
+                    }
+                }
+                const uint32_t e = crc_emit<W, (N < 32 ? N : 32), 8>(vs, zs, p, a.msg ? a.msg + cw * K : nullptr, mw,
+                                                                     K - a.crc_c);
+                if (a.uhat) {
+                    float* urow = a.uhat + cw * N;
+#pragma unroll
+                    for (int k = 0; k < N; ++k) {
+                        const uint32_t sb = (us[k >> 5] >> (k & 31)) & 1u, zb = (zs[k >> 5] >> (k & 31)) & 1u;
+                        urow[k] = zb ? 0.0f : (sb ? -1.0f : 1.0f);
+                    }
+                }
+                if (a.crc_ok) a.crc_ok[cw] = anyp ? 1 : 0;
+                err_bits += e;
+                err_blocks += e ? 1u : 0u;
+                err_crc += anyp ? 0u : 1u;
+            }
+            continue;
+        }
+
         // ---- ML choice (polar.py:868-874): codeword of each path from its decision bits
         uint32_t S[W], Z[W];
 #pragma unroll
@@ -1005,15 +1207,19 @@ __global__ __launch_bounds__(64) void scl_lds_kernel(const CodeParams p, const A
             atomicAdd(a.counters + 0, (unsigned long long)eb);
             atomicAdd(a.counters + 1, (unsigned long long)bl);
         }
+        if constexpr (CRC) {
+            const uint32_t cf = wave_sum_u32(err_crc);
+            if (lane == 0) atomicAdd(a.counters + 2, (unsigned long long)cf);
+        }
     }
 }
 
-template <int N, int G, bool PAC>
+template <int N, int G, bool PAC, bool CRC = false>
 static int launch_lds(const CodeParams& p, Args a, hipStream_t s) {
     constexpr int T = 64 / G;
     const size_t lds = (size_t)(G > 8 ? LdsRows<N>::kRowsWide : LdsRows<N>::kRows) * kWave * sizeof(float);
     a.ntiles = (a.B + T - 1) / T;
-    auto kern = scl_lds_kernel<N, G, PAC>;
+    auto kern = scl_lds_kernel<N, G, PAC, CRC>;
     static bool attr_set = false;  // benign race (idempotent)
     if (!attr_set && lds > 65536) {
         NPD_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 163840));
@@ -1029,43 +1235,43 @@ static int launch_lds(const CodeParams& p, Args a, hipStream_t s) {
     return launch_check("scl_lds_kernel launch");
 }
 
-template <int N, bool PAC>
+template <int N, bool PAC, bool CRC = false>
 static int launch_lds_n(const CodeParams& p, const Args& a, hipStream_t s) {
-    if (a.L == 1) return launch_lds<N, 1, PAC>(p, a, s);
-    if (a.L == 2) return launch_lds<N, 2, PAC>(p, a, s);
-    if (a.L <= 4) return launch_lds<N, 4, PAC>(p, a, s);
-    return launch_lds<N, 8, PAC>(p, a, s);
+    if (a.L == 1) return launch_lds<N, 1, PAC, CRC>(p, a, s);
+    if (a.L == 2) return launch_lds<N, 2, PAC, CRC>(p, a, s);
+    if (a.L <= 4) return launch_lds<N, 4, PAC, CRC>(p, a, s);
+    return launch_lds<N, 8, PAC, CRC>(p, a, s);
 }
 
 // the kernel for p.N (8 .. 256, checked by the caller) and a.L (1 .. 8; larger lists go to dispatch_wide)
-template <bool PAC>
+template <bool PAC, bool CRC = false>
 static int dispatch(const CodeParams& p, const Args& a, hipStream_t s) {
     switch (p.N) {
-        case 8: return launch_n<8, PAC>(p, a, s);
-        case 16: return launch_n<16, PAC>(p, a, s);
-        case 32: return launch_n<32, PAC>(p, a, s);
-        case 64: return launch_n<64, PAC>(p, a, s);
-        case 128: return launch_lds_n<128, PAC>(p, a, s);
-        default: return launch_lds_n<256, PAC>(p, a, s);
+        case 8: return launch_n<8, PAC, CRC>(p, a, s);
+        case 16: return launch_n<16, PAC, CRC>(p, a, s);
+        case 32: return launch_n<32, PAC, CRC>(p, a, s);
+        case 64: return launch_n<64, PAC, CRC>(p, a, s);
+        case 128: return launch_lds_n<128, PAC, CRC>(p, a, s);
+        default: return launch_lds_n<256, PAC, CRC>(p, a, s);
     }
 }
 
 // the kernel for p.N (8 .. 256) and a.L (9 .. 32): G = 16 up to 16 paths, G = 32 above
-template <int N, bool PAC>
+template <int N, bool PAC, bool CRC = false>
 static int launch_wide_n(const CodeParams& p, const Args& a, hipStream_t s) {
-    if (a.L <= 16) return launch_lds<N, 16, PAC>(p, a, s);
-    return launch_lds<N, 32, PAC>(p, a, s);
+    if (a.L <= 16) return launch_lds<N, 16, PAC, CRC>(p, a, s);
+    return launch_lds<N, 32, PAC, CRC>(p, a, s);
 }
 
-template <bool PAC>
+template <bool PAC, bool CRC = false>
 static int dispatch_wide(const CodeParams& p, const Args& a, hipStream_t s) {
     switch (p.N) {
-        case 8: return launch_wide_n<8, PAC>(p, a, s);
-        case 16: return launch_wide_n<16, PAC>(p, a, s);
-        case 32: return launch_wide_n<32, PAC>(p, a, s);
-        case 64: return launch_wide_n<64, PAC>(p, a, s);
-        case 128: return launch_wide_n<128, PAC>(p, a, s);
-        default: return launch_wide_n<256, PAC>(p, a, s);
+        case 8: return launch_wide_n<8, PAC, CRC>(p, a, s);
+        case 16: return launch_wide_n<16, PAC, CRC>(p, a, s);
+        case 32: return launch_wide_n<32, PAC, CRC>(p, a, s);
+        case 64: return launch_wide_n<64, PAC, CRC>(p, a, s);
+        case 128: return launch_wide_n<128, PAC, CRC>(p, a, s);
+        default: return launch_wide_n<256, PAC, CRC>(p, a, s);
     }
 }
 
@@ -1074,6 +1280,11 @@ int run_pac(const CodeParams& p, const Args& a, hipStream_t s);
 // npd_scl_wide.hip / npd_scl_pac_wide.hip: list sizes 9 .. 32, Polar / PAC
 int run_wide(const CodeParams& p, const Args& a, hipStream_t s);
 int run_pac_wide(const CodeParams& p, const Args& a, hipStream_t s);
+// npd_scl_crc_pac.hip / npd_scl_crc_wide.hip / npd_scl_crc_pac_wide.hip: the CRC-aided instantiations other than
+// Polar with 1 .. 8 paths (those are in npd_scl_crc.hip, with the C ABI)
+int run_crc_pac(const CodeParams& p, const Args& a, hipStream_t s);
+int run_crc_wide(const CodeParams& p, const Args& a, hipStream_t s);
+int run_crc_pac_wide(const CodeParams& p, const Args& a, hipStream_t s);
 
 }  // namespace scl
 }  // namespace npd

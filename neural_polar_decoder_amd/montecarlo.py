@@ -98,7 +98,7 @@ class MonteCarlo:
         d = _dist()
         if d is not None and self.world > 1:
             d.all_reduce(counters)  # the one collective of the run
-        c = counters.cpu().numpy()
+        c = self.last_counters = counters.cpu().numpy()  # every column, for drivers that count more than two things
         return MCResult(self.snrs, [int(v) for v in c[:, 0]], [int(v) for v in c[:, 1]], self.total, self.K)
 
 
@@ -149,6 +149,33 @@ class SCLMonteCarlo(SCMonteCarlo):
 
     def count_sweep(self, cw_offset, n, counters):
         return MonteCarlo.count_sweep(self, cw_offset, n, counters)
+
+
+class CASCLMonteCarlo(SCLMonteCarlo):
+    """CRC-aided SC-List decoding of a PolarCode or a PAC whose CRC is set (code.set_crc): generate with the CRC
+    (npd_mc_generate_crc) + npd_scl_decode_crc_mc (decode, choose by CRC and count in one launch).  The errors are
+    counted over the K - CRC_len message bits (MCResult.K); the third counter is the words no list path passed for
+    (``crc_fail``, one per SNR point, set by run())."""
+
+    def __init__(self, code, list_size, snrs, total_cw, batch, seed=1234, rank=None, world=None, device=None):
+        if not getattr(code, "CRC_len", 0):
+            raise ValueError("CASCLMonteCarlo needs a code with a CRC: call code.set_crc(CRC_len) first")
+        super().__init__(code, list_size, snrs, total_cw, batch, seed, rank, world, device)
+        self.K = code.K_minus_CRC
+        self.crc_len = code.CRC_len
+        self.crc_fail = None
+
+    def new_counters(self):
+        return torch.zeros(len(self.snrs), 3, dtype=torch.int64, device=self.device)
+
+    def count_batch(self, si, snr, cw_offset, n, counters_row):
+        _, _, y = self.code.mc_generate_crc(n, snr, self.seed, si, cw_offset, device=self.device, want_msg=False)
+        self.code.scl_decode_crc_mc(y, snr, self.list_size, self.seed, cw_offset, counters_row)
+
+    def run(self) -> MCResult:
+        res = super().run()
+        self.crc_fail = [int(v) for v in self.last_counters[:, 2]]
+        return res
 
 
 class LSEMonteCarlo(SCMonteCarlo):
@@ -332,6 +359,9 @@ def _parse_args(argv=None):
     ap.add_argument("--batch_size", type=int, default=1 << 20)
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--list_size", type=int, default=None, help="also run SC-List with this list size, 1 .. 32 (Polar and PAC)")
+    ap.add_argument("--crc_len", type=int, default=None, choices=[3, 6, 8, 11, 16, 24],
+                    help="with --list_size: also run CRC-aided SC-List with a CRC of this many bits "
+                         "(CRC_polynomials; the message shrinks to K - crc_len bits)")
     ap.add_argument("--lse", action="store_true", help="also run the exact-LSE sc_decode (Polar, polar.py:209)")
     ap.add_argument("--hard_decision", action="store_true", help="exact-LSE SC with sign decisions (else tanh)")
     ap.add_argument("--ml", action="store_true", help="also run maximum-likelihood decoding over the codebook "
@@ -350,6 +380,11 @@ def _parse_args(argv=None):
     ap.add_argument("--embed_dim", type=int, default=128, help="--conv without checkpoint: channels")
     ap.add_argument("--init_seed", type=int, default=0, help="torch seed of the untrained (seeded) decoder weights")
     a = ap.parse_args(argv)
+    if a.crc_len is not None:
+        if not a.list_size:
+            ap.error("--crc_len needs --list_size (it chooses among the list's paths)")
+        if a.crc_len >= a.K:
+            ap.error("--crc_len must be below K")
     if a.rnn_list_size is not None:
         if not a.crisp:
             ap.error("--rnn_list_size needs --crisp (it list-decodes with the CRISP GRU)")
@@ -382,6 +417,12 @@ def _main(argv=None):
     scl = None
     if a.list_size:
         scl = SCLMonteCarlo(code, a.list_size, snrs, a.test_size, a.batch_size, a.seed).run()
+    cascl = cascl_fail = None
+    if a.list_size and a.crc_len:
+        code.set_crc(a.crc_len)
+        drv = CASCLMonteCarlo(code, a.list_size, snrs, a.test_size, a.batch_size, a.seed)
+        cascl, cascl_fail = drv.run(), drv.crc_fail
+        code.set_crc(0)
     lse = None
     if a.lse:
         if a.code != "polar":
@@ -438,6 +479,10 @@ def _main(argv=None):
             print("BERs of SCL decoding: {0}".format(scl.ber))
             print("BLERs of SCL decoding: {0}".format(scl.bler))
             rec["scl"] = dict(scl.as_dict(), list_size=a.list_size)
+        if cascl is not None:
+            print("BERs of CRC-aided SCL decoding: {0}".format(cascl.ber))
+            print("BLERs of CRC-aided SCL decoding: {0}".format(cascl.bler))
+            rec["ca_scl"] = dict(cascl.as_dict(), list_size=a.list_size, crc_len=a.crc_len, crc_fail=cascl_fail)
         if lse is not None:
             print("BERs of exact-LSE SC decoding: {0}".format(lse.ber))
             print("BLERs of exact-LSE SC decoding: {0}".format(lse.bler))

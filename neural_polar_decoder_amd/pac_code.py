@@ -18,7 +18,7 @@ import torch
 from . import _lib
 from . import polar as _ml
 from .codes import pac_info_positions
-from .polar import _aligned, _CodeHandle, _Philox
+from .polar import _NO_CRC, _aligned, _CodeHandle, _CRCSurface, _Philox
 import ctypes
 
 from .utils import llr_scale, sigma_f32
@@ -32,7 +32,7 @@ def dec2bitarray(in_number, bit_width):
     return bits
 
 
-class PAC:
+class PAC(_CRCSurface):
     def __init__(self, args, N, K, g, infty=1000., rate_profile="RM"):
         self.N = N
         self.n = int(np.log2(N))
@@ -69,6 +69,9 @@ class PAC:
         if h is None:
             h = self._codes[key] = _CodeHandle(self.N, np.asarray(key), self.g, self.infty)
         return h
+
+    def _crc_handle(self) -> _CodeHandle:
+        return self._code_for(self.B)
 
     def manual_seed(self, seed: int):
         self._rng = _Philox(seed)
@@ -161,10 +164,12 @@ class PAC:
 
     def scl_decode(self, corrupted_codewords, snr, L=1, use_CRC=False, want_llrs=True):
         """PolarCode.scl_decode's signature and return for a PAC code: (leaf LLRs of the chosen path (B,N) or
-        None, msg_hat = v_hat[:, B] (B,K)) of pac_scl_decode."""
+        None, msg_hat = v_hat[:, B] (B,K)) of pac_scl_decode.  ``use_CRC=True`` after set_crc / encode_with_crc is
+        scl_decode_crc (the CRC covers the message before the convolution): msg_hat is then (B, K - CRC_len)."""
         if use_CRC:
-            raise NotImplementedError("scl_decode(use_CRC=True) depends on module globals of the reference "
-                                      "(polar.py:741-763: `polar.CRC_len`); only the use_CRC=False path is built")
+            if not self.CRC_len:
+                raise NotImplementedError(_NO_CRC)
+            return self.scl_decode_crc(corrupted_codewords, snr, L, want_llrs)
         llr, vh, _ = self.pac_scl_decode(corrupted_codewords, snr, L, want_llrs)
         return llr, vh
 

@@ -68,7 +68,146 @@ class _Philox:
         return o
 
 
-class PolarCode:
+def crc_degree(poly: int) -> int:
+    """Degree of a CRC polynomial given as an integer (bit i = coefficient of x^i)."""
+    return int(poly).bit_length() - 1
+
+
+class _CRCSurface:
+    """CRC-aided SC-List decoding, shared by PolarCode and PAC (include/npd.h, "CRC-aided SC-List decode").
+
+    The reference declares this surface (``CRC_polynomials``, ``get_CRC``, ``CRC_check``, ``encode_with_crc``,
+    ``scl_decode(..., use_CRC=True)``, polar.py:113-117, :738-775, :849-866) but its helpers do not run; the CRC and
+    the selection rule are the ones npd.h defines.  Polynomials are integers, bit i = coefficient of x^i:
+
+      3: 0xB        x^3 + x + 1                                  (reference)
+      8: 0x1D5      x^8 + x^7 + x^6 + x^4 + x^2 + 1              (reference)
+     16: 0x11021    x^16 + x^12 + x^5 + 1                        (reference)
+      6: 0x61       x^6 + x^5 + 1                                (5G NR CRC6)
+     11: 0xE21      x^11 + x^10 + x^9 + x^5 + 1                  (5G NR CRC11)
+     24: 0x1B2B117  x^24 + x^23 + x^21 + x^20 + x^17 + x^15 + x^13 + x^12 + x^8 + x^4 + x^2 + x + 1  (5G NR CRC24C)
+
+    Symbol -1 is bit 1.  The K message columns carry K - CRC_len message symbols, then the CRC.  A subclass
+    provides ``_crc_handle()`` (its code handle) and ``encode``."""
+
+    CRC_polynomials = {3: 0xB, 8: 0x1D5, 16: 0x11021, 6: 0x61, 11: 0xE21, 24: 0x1B2B117}
+    CRC_len = 0
+    crc_poly = 0
+
+    def set_crc(self, CRC_len, poly=None):
+        """Choose the CRC: ``CRC_len`` bits with polynomial ``poly`` (default ``CRC_polynomials[CRC_len]``); sets
+        ``CRC_len`` and ``K_minus_CRC``.  ``CRC_len = 0`` clears it.  ValueError for a length or polynomial that
+        npd.h's rules exclude (1 <= degree <= 24, bit 0 set, degree < K, degree == CRC_len)."""
+        c = int(CRC_len)
+        K = int(self.K)
+        if c == 0:
+            if poly not in (None, 0):
+                raise ValueError("CRC_len = 0 clears the CRC and takes no polynomial")
+            self.CRC_len, self.crc_poly, self.K_minus_CRC = 0, 0, K
+            return
+        if poly is None:
+            if c not in self.CRC_polynomials:
+                raise ValueError(f"no default polynomial of degree {c}: CRC_polynomials has {sorted(self.CRC_polynomials)}")
+            poly = self.CRC_polynomials[c]
+        poly = int(poly)
+        if poly <= 0 or poly >= 1 << 32 or crc_degree(poly) != c:
+            raise ValueError(f"polynomial {poly:#x} does not have degree CRC_len = {c}")
+        if not 1 <= c <= 24:
+            raise ValueError("CRC_len must be 1 .. 24")
+        if not poly & 1:
+            raise ValueError(f"polynomial {poly:#x}: the constant coefficient (bit 0) must be set")
+        if c >= K:
+            raise ValueError(f"CRC_len = {c} leaves no message bit of K = {K}")
+        self.CRC_len, self.crc_poly, self.K_minus_CRC = c, poly, K - c
+
+    def _need_crc(self):
+        if not self.CRC_len:
+            raise ValueError("no CRC is set: call set_crc(CRC_len) or encode_with_crc(message, CRC_len) first")
+        return self._crc_handle()
+
+    def crc_attach(self, message):
+        """(batch, K - CRC_len) symbols -> (batch, K): the message unchanged, then its CRC as +-1 (bit = message < 0)."""
+        h = self._need_crc()
+        msg = _lib.f32c(_lib.stage(message, "message"))
+        if msg.dim() != 2 or msg.shape[1] != self.K_minus_CRC:
+            raise ValueError(f"message must be (batch, {self.K_minus_CRC}), got {tuple(msg.shape)}")
+        out = torch.empty(msg.shape[0], h.K, dtype=torch.float32, device=msg.device)
+        _lib.check(_lib.load().npd_crc_attach(_lib.ptr(msg), _lib.ptr(out), msg.shape[0], h.K, self.crc_poly,
+                                              _lib.stream_of(msg.device)), "npd_crc_attach")
+        return _lib.home(out, message)
+
+    def encode_with_crc(self, message, CRC_len):
+        """PolarCode.encode_with_crc (polar.py:765-775): set the CRC, then encode [message, CRC]; CRC_len = 0 is the
+        plain encoder."""
+        self.set_crc(CRC_len)
+        if self.CRC_len == 0:
+            return self.encode(message)
+        return self.encode(self.crc_attach(message))
+
+    def mc_generate_crc(self, B, snr, seed, snr_index=0, cw_offset=0, device=None, want_msg=True, want_x=False, out=None):
+        """mc_generate whose last CRC_len message columns are the CRC of the first K - CRC_len (which, like the noise,
+        are exactly mc_generate's); msg is (B, K)."""
+        h = self._need_crc()
+        device = torch.device(device or "cuda") if out is None else out.device
+        if out is not None:
+            _lib.check_out(out, "out", torch.float32, B * h.N, device)
+        y = torch.empty(B, h.N, dtype=torch.float32, device=device) if out is None else out
+        msg = torch.empty(B, h.K, dtype=torch.float32, device=device) if want_msg else None
+        x = torch.empty(B, h.N, dtype=torch.float32, device=device) if want_x else None
+        _lib.check(_lib.load().npd_mc_generate_crc(h.h, self.crc_poly, _lib.ptr(msg), _lib.ptr(x), _lib.ptr(y), B,
+                                                   sigma_f32(snr), int(seed), int(snr_index), int(cw_offset),
+                                                   _lib.stream_of(device)), "npd_mc_generate_crc")
+        return msg, x, y
+
+    def scl_decode_crc(self, corrupted_codewords, snr, L=1, want_llrs=True, return_ok=False, return_all=False):
+        """CRC-aided SC-List decoding with L = 1 .. 32 paths: the passing path of smallest metric, or the path of
+        smallest metric when none passes.  Returns (leaf LLRs of the chosen path (B,N) -- a genie SC pass with its
+        decisions, or None with ``want_llrs=False`` --, msg_hat[:, :K - CRC_len]), plus crc_ok (B) int32 with
+        ``return_ok=True``.  ``return_all=True`` returns (leaf, msg_hat (B,K), u_hat (B,N), crc_ok) instead."""
+        h = self._need_crc()
+        y = _aligned(_lib.f32c(_lib.stage(corrupted_codewords, "corrupted_codewords")))
+        if y.dim() != 2 or y.shape[1] != h.N:
+            raise ValueError(f"corrupted_codewords must be (batch, {h.N}), got {tuple(y.shape)}")
+        B = y.shape[0]
+        hat = torch.empty(B, h.K, dtype=torch.float32, device=y.device)
+        uh = torch.empty(B, h.N, dtype=torch.float32, device=y.device) if (want_llrs or return_all) else None
+        ok = torch.empty(B, dtype=torch.int32, device=y.device) if (return_ok or return_all) else None
+        st = _lib.stream_of(y.device)
+        _lib.check(_lib.load().npd_scl_decode_crc(h.h, _lib.ptr(y), llr_scale(snr), int(L), self.crc_poly, _lib.ptr(hat),
+                                                  _lib.ptr(uh), _lib.ptr(ok), B, st), "npd_scl_decode_crc")
+        leaf = None
+        if want_llrs:
+            leaf = torch.empty(B, h.N, dtype=torch.float32, device=y.device)
+            _lib.check(_lib.load().npd_sc_decode(h.h, _lib.ptr(y), llr_scale(snr), _lib.ptr(leaf), None, None,
+                                                 _lib.ptr(uh), B, st), "npd_sc_decode (genie leaf LLRs)")
+        c = corrupted_codewords
+        if return_all:
+            return _lib.home(leaf, c), _lib.home(hat, c), _lib.home(uh, c), _lib.home(ok, c)
+        out = (_lib.home(leaf, c), _lib.home(hat[:, :self.K_minus_CRC], c))
+        return out + (_lib.home(ok, c),) if return_ok else out
+
+    def scl_decode_crc_mc(self, y, snr, L, seed, cw_offset, counters, msg_hat=None):
+        """counters[0..2] += {bit errors, block errors over the K - CRC_len message bits against the Philox messages of
+        codewords cw_offset .. cw_offset + batch - 1, words no path passed for}, decoded and counted in one launch."""
+        h = self._need_crc()
+        _lib.require_gpu(y, "y")
+        if y.dim() != 2 or y.shape[1] != h.N:
+            raise ValueError(f"y must be (batch, {h.N}), got {tuple(y.shape)}")
+        _lib.check_out(counters, "counters", torch.int64, 3, y.device)
+        _lib.check_out(msg_hat, "msg_hat", torch.float32, y.shape[0] * h.K, y.device, optional=True)
+        y = _aligned(_lib.f32c(y))
+        _lib.check(_lib.load().npd_scl_decode_crc_mc(h.h, _lib.ptr(y), llr_scale(snr), int(L), self.crc_poly,
+                                                     _lib.ptr(msg_hat), int(seed), int(cw_offset), y.shape[0],
+                                                     _lib.ptr(counters), _lib.stream_of(y.device)),
+                   "npd_scl_decode_crc_mc")
+        return counters
+
+
+_NO_CRC = ("scl_decode(use_CRC=True) needs a CRC: call set_crc(CRC_len) or encode_with_crc(message, CRC_len) first "
+           "(the reference's own helpers, polar.py:738-763, read a module global and do not run)")
+
+
+class PolarCode(_CRCSurface):
     def __init__(self, n, K, args=None, F=None, rs=None, use_cuda=True, infty=1000.):
         assert n >= 1
         self.args = args
@@ -105,6 +244,9 @@ class PolarCode:
         if self._code is None:
             self._code = _CodeHandle(self.N, self.info_positions, 0, self.infty)
         return self._code
+
+    def _crc_handle(self) -> _CodeHandle:
+        return self.code
 
     def _code_for(self, info_positions) -> _CodeHandle:
         if info_positions is None:
@@ -175,10 +317,12 @@ class PolarCode:
         """SC-List decoding with L = 1 .. 32 paths; returns (leaf LLRs of the chosen path (B,N), msg_hat (B,K)).
 
         The chosen path's leaf LLRs are recomputed by a genie SC pass with its decisions (identical
-        values); ``want_llrs=False`` skips that pass and returns None in their place."""
+        values); ``want_llrs=False`` skips that pass and returns None in their place.  ``use_CRC=True`` after set_crc /
+        encode_with_crc is scl_decode_crc: msg_hat is then the (B, K - CRC_len) message of the CRC-chosen path."""
         if use_CRC:
-            raise NotImplementedError("scl_decode(use_CRC=True) depends on module globals of the reference "
-                                      "(polar.py:741-763: `polar.CRC_len`); only the use_CRC=False path is built")
+            if not self.CRC_len:
+                raise NotImplementedError(_NO_CRC)
+            return self.scl_decode_crc(corrupted_codewords, snr, L, want_llrs)
         y = _aligned(_lib.f32c(_lib.stage(corrupted_codewords, "corrupted_codewords")))
         B = y.shape[0]
         hat = torch.empty(B, self.K, dtype=torch.float32, device=y.device)
