@@ -321,6 +321,8 @@ int npd_count_errors_masked(const float* ref, const float* hat, const int64_t* m
  * then linear.weight (F) | linear.bias (1); Din_0 = N + 2 (onehot) or N + 1, Din_l = F for l > 0.
  * precision: 0 = fp32 (default, exact fp32 FMA chains), 1 = bf16x3 split, 2 = bf16, 3 = fp16x3 split (hi + lo fp16
  * parts, three products per multiply, fp32 accumulation: held to the fp32 path's tolerance; F <= 64).
+ * N: a multiple of 8 in [8, 256] (split precisions: of 16).  F > 64 keeps both layers' states and the tile's y in LDS,
+ * (layers F + N + min(F / 32, 8)) * 128 bytes <= 160 KiB: only F = 512 with 2 layers is bounded by it, to N <= 248.
  */
 int npd_gru_create(int N, int F, int layers, int onehot, const float* weights, int64_t n_weights, int precision,
                    npd_gru** out);
@@ -329,9 +331,9 @@ int npd_gru_destroy(npd_gru* gru);
  * npd_gru_create for either cell of rnn_all.py:69 (--rnn_type GRU | LSTM): cell 0 = GRU (npd_gru_create), cell 1 =
  * LSTM (nn.LSTM, gates i, f, g, o; the same weight order with 4F gate rows: weight_ih_l (4F, Din_l) | weight_hh_l (4F, F)
  * | bias_ih_l (4F) | bias_hh_l (4F) per layer, then linear.weight | linear.bias).  LSTM: fp32 (precision 0), hidden
- * 32, 64, 128, 256 or 512, 1 or 2 layers (F = 512 with 2 layers: N <= 128, as the GRU), y_input decoding (npd_gru_decode) or
- * y_h0 decoding (npd_gru_decode_ex with y = NULL: h and c both start from h0, as get_h0 returns (x, x) for LSTM,
- * rnn_all.py:370-375); destroy with npd_gru_destroy.
+ * 32, 64, 128, 256 or 512, 1 or 2 layers (F = 512 with 2 layers: N <= 248, the GRU's LDS bound), y_input decoding
+ * (npd_gru_decode) or y_h0 decoding (npd_gru_decode_ex with y = NULL: h and c both start from h0, as get_h0 returns
+ * (x, x) for LSTM, rnn_all.py:370-375); destroy with npd_gru_destroy.
  */
 int npd_rnn_create(int cell, int N, int F, int layers, int onehot, const float* weights, int64_t n_weights, int precision,
                    npd_gru** out);
@@ -375,8 +377,9 @@ int npd_gru_decode_ex(const npd_gru* gru, const float* y, const float* h0, const
  * then errors_ber / errors_bler(msg, decoded[:, info]), rnn_all.py:874-879, utils.py:17-51): y is (n_seg, B, N), one
  * segment of received words per SNR point; msg (B, K) the message bits of the B codewords (the same messages in every
  * segment: the Monte-Carlo driver's message stream is keyed by codeword, not SNR); cols (K, HOST) the decoded columns
- * compared with msg's columns.  counters (n_seg, 2) += [bit errors, block errors] of each segment -- equal, count for
- * count, to npd_gru_decode_ex + npd_count_errors_cols per segment.  decoded (n_seg, B, N) is optional for the
+ * compared with msg's columns, K <= N distinct positions in any order (a repeat is NPD_EINVAL; K = N = 256 compares
+ * every position, message column 255 included).  counters (n_seg, 2) += [bit errors, block errors] of each segment --
+ * equal, count for count, to npd_gru_decode_ex + npd_count_errors_cols per segment.  decoded (n_seg, B, N) is optional for the
  * 16-codeword split kernel (F = 64, 2 layers, N % 32 == 0, precision != 0), which decodes and counts every segment in
  * ONE launch (errors counted in the decision epilogue, one atomic pair per wave and segment); other handles run one
  * decode + one count per segment and need decoded.  y_input decoding, no gt, no logits.

@@ -62,7 +62,8 @@ extern "C" int npd_rnn_create(int cell, int N, int F, int layers, int onehot, co
     NPD_ARG(F == 32 || F == 64 || F == 128 || F == 256 || F == 512,
             "npd_rnn_create: LSTM hidden size F must be 32, 64, 128, 256 or 512");
     NPD_ARG(F <= 64 || gru::wide_lds_bytes(N, F, layers) <= 160 * 1024,
-            "npd_rnn_create: an LSTM with F = 512 and 2 layers needs N <= 128 (LDS holds both states and the tile's y)");
+            "npd_rnn_create: an LSTM with F = 512 and 2 layers needs N <= 248 (the 160 KiB of LDS hold both states and "
+            "the tile's y)");
     NPD_ARG(precision == 0, "npd_rnn_create: LSTM cells run fp32 (precision 0)");
     NPD_ARG(n_weights == weight_count(4, N, F, layers, onehot),
             "npd_rnn_create: weight count does not match (LSTM, N, F, layers, onehot)");
@@ -139,7 +140,8 @@ extern "C" int npd_gru_create(int N, int F, int layers, int onehot, const float*
             "npd_gru_create: hidden size F must be 32, 64, 128, 256 or 512");
     NPD_ARG(F <= 64 || precision == 0, "npd_gru_create: the bf16 kernels cover F <= 64; F > 64 runs fp32");
     NPD_ARG(F <= 64 || gru::wide_lds_bytes(N, F, layers) <= 160 * 1024,
-            "npd_gru_create: F = 512 with 2 layers needs N <= 128 (LDS holds both states and the tile's y)");
+            "npd_gru_create: F = 512 with 2 layers needs N <= 248 (the 160 KiB of LDS hold both states and the tile's "
+            "y)");
     NPD_ARG(layers == 1 || layers == 2, "npd_gru_create: 1 or 2 GRU layers supported");
     NPD_ARG(precision >= 0 && precision <= 3,
             "npd_gru_create: precision must be 0 (fp32), 1 (bf16x3), 2 (bf16) or 3 (fp16x3)");
@@ -207,11 +209,13 @@ extern "C" int npd_gru_decode_count_sweep(const npd_gru* g, int n_seg, const flo
             "npd_gru_decode_count_sweep: null pointer");
     NPD_ARG(((uintptr_t)y & 15) == 0, "npd_gru_decode_count_sweep: y must be 16-byte aligned");
     NPD_ARG(K <= g->N, "npd_gru_decode_count_sweep: K > N");
-    uint8_t slot[kMaxN];
-    memset(slot, 255, sizeof(slot));  // TODO: slot 255 is also message 255 at K = 256
+    // slot: the message column a position is compared with; cmp: the mask of the compared positions (as Args::info)
+    uint8_t slot[kMaxN] = {};
+    uint32_t cmp[kMaxWords] = {};
     for (int k = 0; k < K; ++k) {
         NPD_ARG(cols[k] >= 0 && cols[k] < g->N, "npd_gru_decode_count_sweep: column out of range");
-        NPD_ARG(slot[cols[k]] == 255, "npd_gru_decode_count_sweep: repeated column");
+        NPD_ARG(!((cmp[cols[k] >> 5] >> (cols[k] & 31)) & 1u), "npd_gru_decode_count_sweep: repeated column");
+        cmp[cols[k] >> 5] |= 1u << (cols[k] & 31);
         slot[cols[k]] = (uint8_t)k;
     }
     if (g->img16 == nullptr || g->cell != 0) {
@@ -229,7 +233,7 @@ extern "C" int npd_gru_decode_count_sweep(const npd_gru* g, int n_seg, const flo
         return NPD_OK;
     }
     const gru::Args a = make_args(g, y, nullptr, is_info, reverse, nullptr, decoded, nullptr, B);
-    return gru::launch_split16_sweep(g, a, n_seg, msg, K, slot, counters, (hipStream_t)stream);
+    return gru::launch_split16_sweep(g, a, n_seg, msg, K, slot, cmp, counters, (hipStream_t)stream);
 }
 
 extern "C" int npd_gru_decode(const npd_gru* g, const float* y, const uint8_t* is_info, int reverse, const float* gt,

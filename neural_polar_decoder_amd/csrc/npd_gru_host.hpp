@@ -121,9 +121,11 @@ int launch_lstm(const npd_gru* g, const Args& a, hipStream_t s);
 void build_image_split(npd_gru& g, const float* W, HostImages& im);
 void build_image_split16(npd_gru& g, const float* W, HostImages& im);
 int launch_split(const npd_gru* g, const Args& a, hipStream_t s);
-// sweep / count mode of the 16-codeword kernel (a.y, a.decoded: n_seg segments; slot: message slot per position)
+// sweep / count mode of the 16-codeword kernel (a.y, a.decoded: n_seg segments; slot: message slot per position, cmp: the
+// mask of the compared positions, laid out as Args::info)
 int launch_split16_sweep(const npd_gru* g, const Args& a, int n_seg, const float* msg, int K,
-                         const uint8_t (&slot)[kMaxN], unsigned long long* counters, hipStream_t s);
+                         const uint8_t (&slot)[kMaxN], const uint32_t (&cmp)[kMaxWords], unsigned long long* counters,
+                         hipStream_t s);
 // npd_gru_wide.hip: F >= 128, and the LSTM at F = 64 x 2
 int wide_lds_bytes(int N, int F, int L);
 int launch_wide(const npd_gru* g, const Args& a, hipStream_t s);

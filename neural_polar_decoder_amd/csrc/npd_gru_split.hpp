@@ -56,13 +56,14 @@ struct ArgsB {
     int64_t wy_lo;  // offset (in f4) of the lo Wy image
     uint32_t info[kMaxWords];
     // sweep / count mode (gru16p_kernel only): y, decoded and logits are nseg segments of (B, N) back to back; with
-    // counters != NULL the decision at position jj is compared with msg[cw][slot[jj]] (slot 255: not compared) and
+    // counters != NULL the decision at every position jj of the mask cmp is compared with msg[cw][slot[jj]] and
     // counters[2 s], [2 s + 1] += bit / block errors of segment s (npd_gru_decode_count_sweep)
     const float* msg;
     unsigned long long* counters;
     int K;
     int nseg;
     uint32_t slotw[kMaxN / 4];  // byte jj & 3 of word jj >> 2 = slot of position jj (copied to the LDS step table)
+    uint32_t cmp[kMaxWords];    // bit jj & 31 of word jj >> 5: position jj is compared (as info; all slot values are slots)
 };
 
 static uint16_t bf16_rne(float f) {

@@ -31,7 +31,8 @@ struct Geo16 {
     static constexpr int C0L0 = OFF_C, C1L0 = OFF_C + 192, BHN0 = OFF_C + 384, C0L1 = OFF_C + 448,
                          BHN1 = OFF_C + 640, WLIN = OFF_C + 704, TOTAL = OFF_C + 768;
     // behind the image in LDS, written by every block from the kernel arguments: one word per step in DECODE order
-    // (rev applied), bits 0-7 the position's message slot (255: not compared), bit 8 its is-information bit
+    // (rev applied), bits 0-7 the position's message slot, bit 8 its is-information bit, bit 9 set where the decision
+    // is compared with the message (a bit of its own: all 256 slot values are slots, K = 256)
     static constexpr int LDS_BYTES = TOTAL * 4 + kMaxN * 4;
 };
 
@@ -194,8 +195,9 @@ __global__ __launch_bounds__(64 * NPD_GRU16_WPB) void gru16p_kernel(const ArgsB 
         uint32_t* tw = reinterpret_cast<uint32_t*>(smem4) + G::TOTAL;
         for (int i = threadIdx.x; i < a.N; i += blockDim.x) {
             const int jj = a.rev ? a.N - 1 - i : i;
-            const uint32_t sl = a.counters ? (a.slotw[jj >> 2] >> (8 * (jj & 3))) & 255u : 255u;
-            tw[i] = sl | (((a.info[jj >> 5] >> (jj & 31)) & 1u) << 8);
+            const uint32_t sl = (a.slotw[jj >> 2] >> (8 * (jj & 3))) & 255u;
+            const uint32_t cmp = a.counters ? (a.cmp[jj >> 5] >> (jj & 31)) & 1u : 0u;
+            tw[i] = sl | (((a.info[jj >> 5] >> (jj & 31)) & 1u) << 8) | (cmp << 9);
         }
         __syncthreads();
     }
@@ -402,7 +404,7 @@ __global__ __launch_bounds__(64 * NPD_GRU16_WPB) void gru16p_kernel(const ArgsB 
                     if constexpr (c == 10) te = __builtin_amdgcn_readfirstlane(tv);
                 } else if constexpr (c == 12) {
                     const bool info = (te >> 8) & 1u;
-                    const uint32_t sl = te & 255u;  // message slot (255: not compared)
+                    const uint32_t sl = te & 255u;  // message slot
                     float d;
                     if constexpr (CNT) {
                         d = 1.0f;  // a frozen position's decision: no output, no reduction, no sign test
@@ -429,7 +431,7 @@ __global__ __launch_bounds__(64 * NPD_GRU16_WPB) void gru16p_kernel(const ArgsB 
                             if (a.logits) a.logits[rowoff + ii] = out;
                         }
                     }
-                    if (sl != 255u) {  // count_errors_kernel's test, rint(msg) != rint(d), on the 2-bit codes
+                    if (te & 512u) {  // compared: count_errors_kernel's test, rint(msg) != rint(d), on the 2-bit codes
                         const uint32_t q = sl >> 2;
                         const uint32_t m01 = (q & 16u) ? mc[1] : mc[0], m23 = (q & 16u) ? mc[3] : mc[2];
                         const uint32_t mw = (q & 32u) ? m23 : m01;
@@ -539,10 +541,12 @@ int launch_split16(const npd_gru* g, const ArgsB& b, hipStream_t s) {
 }
 
 int launch_split16_sweep(const npd_gru* g, const Args& a, int n_seg, const float* msg, int K,
-                         const uint8_t (&slot)[kMaxN], unsigned long long* counters, hipStream_t s) {
+                         const uint8_t (&slot)[kMaxN], const uint32_t (&cmp)[kMaxWords], unsigned long long* counters,
+                         hipStream_t s) {
     ArgsB b = make_args_b(g, a);
     b.msg = msg; b.counters = counters; b.K = K; b.nseg = n_seg;
     memcpy(b.slotw, slot, sizeof(slot));
+    memcpy(b.cmp, cmp, sizeof(cmp));
     return launch_split16(g, b, s);
 }
 

@@ -123,7 +123,7 @@ class RNN_Model(nn.Module):
         common = self.output_size == 1 and head_ok and ln_ok and self.num_rnn_layers in (1, 2)
         if N is not None:
             # npd_gru_create: N a multiple of 8 in [8, 256]; the weight-streaming kernels hold both layers' states and
-            # the tile's y in LDS (gru::wide_lds_bytes), so hidden 512 x 2 layers needs N <= 128
+            # the tile's y in LDS (gru::wide_lds_bytes), so hidden 512 x 2 layers needs N <= 248
             nw = min(fe // 32, 8)
             if not (8 <= N <= 256 and N % 8 == 0):
                 return False

@@ -35,7 +35,9 @@ FIXTURES = ("forced_gru_f32_l1_n16_rev", "forced_gru_f64_l2_n32_onehot", "forced
 
 # family: the kernel the case runs on; head: None (Linear(F, 1)), "ln" (--use_layernorm) or (out_linear_depth, width);
 # bar: the project's logit tolerance of that family / precision (None: plain bf16 has none)
-Case = collections.namedtuple("Case", "id family cell F layers N B onehot rev precision head yh0 g seed bar")
+# ys: a further scale on the y columns of rnn.weight_ih_l0 (LONG_CASES; 1.0: none)
+Case = collections.namedtuple("Case", "id family cell F layers N B onehot rev precision head yh0 g seed bar ys",
+                              defaults=(1.0,))
 
 
 def bar_of(family, precision):
@@ -109,15 +111,79 @@ FAMILY_CASE = {f: next(c for c in CASES if c.family == f and c.bar == bar_of(f, 
 ALTERNATE_LOSS = ("gru_decode-f64x2", "lstm_decode-f32x2")
 
 
+# ---- the long and odd lengths: N up to 256 (the interface's limit), lengths that are no power of two, N = 248 where
+# F = 512 x 2 layers fills the LDS exactly.  What depends on N in the kernels: the k-steps / K blocks of the y projection,
+# the LDS copy of the tile's words, gru16p_kernel's per-step table, the lane-half split, reverse order, and rounding
+# that builds up over 256 recurrent steps.  A table of its own: test_case_table_reaches_every_decode_instantiation counts
+# CASES.  B = 70 (24 where F = 512).
+# A fixed g = 4 does not satisfy the conditions of tests/test_forced_path.py at N = 256: the y projection's variance grows
+# with N (PyTorch draws weight_ih_l0 by the hidden size, not by fan-in), the gates saturate, and E_ref leaves bar / 4 (GRU
+# 64x2: 1.2e-5 against 5e-6); on the LSTMs lowering g alone leaves no window before max |logit| falls below 1.  So a
+# case may scale the y columns of rnn.weight_ih_l0 by ys = sqrt(16 / N) (YS: the projection's variance of N = 16), and
+# each row's (g, ys) is the choice, from g in {4, 3.5, 3.25, 3, 2.6, 2.5} and ys in {1, YS}, that the CPU conditions
+# accept with E_ref well inside bar / 4 -- measured on the CPU with the functions of this file, never on a kernel:
+#   (family, cell, F, layers, N, precision, yh0, g, ys)                              # E_ref forced / genie, max |logit|
+YS = "sqrt(16 / N)"
+LONG_ROWS = [
+    ("gru_decode_kernel", "GRU", 64, 2, 256, "fp32", False, 3.0, YS),                # 2.1e-6 / 2.0e-6, 3.20
+    ("gru_decode_kernel", "GRU", 32, 1, 256, "fp32", False, 3.0, YS),                # 1.5e-6 / 1.4e-6, 4.53
+    ("gru_decode_kernel", "GRU", 64, 1, 24, "fp32", False, 4.0, 1.0),                # 1.3e-6 / 1.5e-6, 4.20
+    ("gru_decode_bf_kernel", "GRU", 32, 2, 256, "fp16x3", False, 2.5, YS),           # 1.5e-6 / 1.1e-6, 2.24
+    ("gru_decode_bf_kernel", "GRU", 32, 2, 256, "bf16x3", False, 4.0, 1.0),          # 2.5e-5 / 1.1e-5, 4.20 (bar 2e-3)
+    ("gru_decode_bf_kernel", "GRU", 64, 1, 256, "fp16x3", False, 3.0, YS),           # 1.3e-6 / 1.2e-6, 2.53
+    ("gru_decode_bf_kernel", "GRU", 64, 1, 256, "bf16x3", False, 4.0, 1.0),          # 5.9e-6 / 6.6e-6, 5.02 (bar 2e-3)
+    ("gru_decode_bf_kernel", "GRU", 32, 1, 48, "fp16x3", False, 4.0, 1.0),           # 2.8e-6 / 2.3e-6, 4.31
+    ("gru16p_kernel", "GRU", 64, 2, 256, "fp16x3", False, 3.0, YS),                  # 2.0e-6 / 2.0e-6, 2.99
+    ("gru16p_kernel", "GRU", 64, 2, 256, "bf16x3", False, 4.0, 1.0),                 # 1.4e-5 / 1.4e-5, 6.34 (bar 2e-3)
+    ("gru16p_kernel", "GRU", 64, 2, 96, "fp16x3", False, 4.0, 1.0),                  # 3.4e-6 / 3.5e-6, 4.17 (nkb = 3)
+    ("gru16p_kernel", "GRU", 64, 2, 160, "fp16x3", False, 3.0, YS),                  # 1.6e-6 / 1.5e-6, 3.12 (nkb = 5)
+    ("gru16p_kernel", "GRU", 64, 2, 256, "fp16x3", True, 4.0, 1.0),                  # 3.3e-6 / 3.5e-6, 3.87 (y_h0)
+    ("gru_wide_kernel", "GRU", 128, 2, 256, "fp32", False, 3.0, YS),                 # 1.6e-6 / 1.9e-6, 3.41
+    ("gru_wide_kernel", "GRU", 512, 1, 256, "fp32", False, 4.0, 1.0),                # 2.7e-6 / 2.7e-6, 2.86
+    ("gru_wide_kernel", "GRU", 256, 1, 40, "fp32", False, 4.0, 1.0),                 # 1.7e-6 / 1.8e-6, 3.75
+    ("gru_wide_kernel", "GRU", 512, 2, 248, "fp32", False, 4.0, 1.0),                # 3.8e-6 / 3.4e-6, 6.29 (LDS full)
+    ("lstm_decode_kernel", "LSTM", 32, 2, 256, "fp32", False, 2.6, YS),              # 1.8e-6 / 2.4e-6, 1.05
+    ("lstm_decode_kernel", "LSTM", 64, 1, 256, "fp32", False, 2.5, YS),              # 6.9e-7 / 7.3e-7, 1.16
+    ("lstm_wide_kernel", "LSTM", 256, 2, 256, "fp32", False, 3.25, YS),              # 1.3e-6 / 1.7e-6, 1.17 (bar 5e-5)
+    ("lstm_wide_kernel", "LSTM", 512, 2, 248, "fp32", False, 3.5, YS),               # 2.4e-6 / 2.4e-6, 1.45 (LDS full)
+]
+
+
+def _long_cases():
+    out = []
+    count = collections.Counter()
+    for family, cell, F, layers, N, precision, yh0, g, ys in LONG_ROWS:
+        i = count[family]
+        count[family] += 1
+        # (onehot, reverse_order) = (1, 0), (0, 1), (1, 1), (0, 0), (1, 0): both values of both in every family
+        onehot, rev = i % 2 == 0, ((i + 1) // 2) % 2 == 1
+        cid = (f"{family.replace('_kernel', '')}-f{F}x{layers}" + (f"-{precision}" if precision != "fp32" else "") +
+               ("-yh0" if yh0 else "") + f"-n{N}")
+        out.append(Case(cid, family, cell, F, layers, N, 24 if F == 512 else 70, onehot, rev, precision, None, yh0,
+                        float(g), 4200 + len(out), bar_of(family, precision),
+                        (16.0 / N) ** 0.5 if ys == YS else float(ys)))
+    return out
+
+
+LONG_CASES = _long_cases()
+# one long case per family for the negative control, B = 1 and rows-past-B tests, chosen as FAMILY_CASE is (B = 70)
+LONG_FAMILY_CASE = {f: next(c for c in LONG_CASES
+                            if c.family == f and c.bar == bar_of(f, "fp32") and not c.yh0 and c.B == 70) for f in FAMILIES}
+CASE_BY_ID.update({c.id: c for c in LONG_CASES})
+
+
 def info_set(N):
-    """The Polar(N, N / 2) information set of the reference (tests/golden/codes.npz, from rnn_all.get_code)."""
+    """The Polar(N, N / 2) information set of the reference (tests/golden/codes.npz, from rnn_all.get_code); where N is
+    not a power of two (no code of the reference has that length), a seeded random half of the positions."""
+    if N & (N - 1):
+        return np.sort(np.random.default_rng(7000 + N).permutation(N)[:N // 2]).astype(np.int64)
     d = np.load(os.path.join(GOLDEN, "codes.npz"))
     return np.asarray(d[f"polar_polar_{N}_{N // 2}_{N // 2}"], np.int64)
 
 
 def build_net(case, device="cpu", g=None):
     """The case's net: RNN_Model under torch.manual_seed(case.seed), LayerNorm's gamma / beta drawn away from (1, 0),
-    then every parameter times g (default case.g)."""
+    then every parameter times g (default case.g), then the y columns of rnn.weight_ih_l0 times case.ys."""
     import torch
     from neural_polar_decoder_amd.rnn import RNN_Model
     torch.manual_seed(case.seed)
@@ -132,6 +198,9 @@ def build_net(case, device="cpu", g=None):
             net.layernorm.bias.uniform_(-0.5, 0.5)
         for p in net.parameters():
             p.mul_(case.g if g is None else float(g))
+        if case.ys != 1.0:
+            assert not case.yh0  # y enters through the y-MLP there, whose Linear(N, .) is drawn by fan-in already
+            net.rnn.weight_ih_l0[:, :case.N].mul_(case.ys)
     return net.to(device).eval()
 
 

@@ -92,7 +92,7 @@ def test_rnn_create_argument_errors():
         ((12, 32, 1, 1, nw(12, 32, 1), 0), b"multiple of 8"),
         ((16, 48, 1, 1, nw(16, 48, 1), 0), b"hidden size F must be"),
         ((16, 128, 1, 1, nw(16, 128, 1), 3), b"cover F <= 64"),
-        ((256, 512, 2, 1, nw(256, 512, 2), 0), b"needs N <= 128"),
+        ((256, 512, 2, 1, nw(256, 512, 2), 0), b"needs N <= 248"),
         ((16, 32, 3, 1, nw(16, 32, 2), 0), b"1 or 2 GRU layers"),
         ((16, 32, 1, 1, nw(16, 32, 1), 4), b"precision must be"),
         ((8, 32, 1, 1, nw(8, 32, 1), 3), b"N % 16"),
@@ -118,7 +118,7 @@ def test_rnn_create_argument_errors():
         ((1, 16, 64, 2, 1, nw(16, 64, 2, gates=4) - 1, 0), b"(LSTM"),
         ((1, 12, 32, 1, 1, nw(12, 32, 1, gates=4), 0), b"multiple of 8"),
         ((1, 16, 48, 1, 1, nw(16, 48, 1, gates=4), 0), b"LSTM hidden size F must be"),
-        ((1, 256, 512, 2, 1, nw(256, 512, 2, gates=4), 0), b"needs N <= 128"),
+        ((1, 256, 512, 2, 1, nw(256, 512, 2, gates=4), 0), b"needs N <= 248"),
         ((1, 16, 32, 3, 1, nw(16, 32, 2, gates=4), 0), b"1 or 2 layers"),
         ((0, 16, 48, 1, 1, nw(16, 48, 1), 0), b"npd_gru_create: hidden size F must be"),   # cell 0: the GRU ladder
     ]
@@ -155,6 +155,34 @@ def test_rnn_create_argument_errors():
         rc = L.npd_rnn_create_ex(cell, N, F, layers, 1, w, n, prec, lw, lb, 1e-5, depth, H, hw, nh, ctypes.byref(out))
         assert rc == -1 and msg in L.npd_last_error() and out.value is None, (cell, F, prec, depth, H, rc,
                                                                              L.npd_last_error())
+
+
+@pytest.mark.gpu
+def test_rnn_create_at_the_lds_limit():
+    """F = 512 with 2 layers keeps (2 F + N + 8) * 128 bytes in LDS: N = 248 is 163 840 bytes, all 160 KiB, and is
+    accepted; N = 256 is refused with NPD_EINVAL before any HIP call; F = 512 with 1 layer takes N = 256.  Both cells,
+    through npd_gru_create and npd_rnn_create.  (An accepted create uploads its images, hence the gpu mark; that the
+    accepted edge also decodes correctly is tests/test_forced_path_gpu.py's N = 248 rows.)"""
+    from neural_polar_decoder_amd import _lib
+    L = _lib.load()
+    assert (2 * 512 + 248 + 8) * 128 == 160 * 1024
+    buf = np.zeros(_rnn_weight_count(4, 256, 512, 2, 1), dtype=np.float32)
+    w = buf.ctypes.data_as(ctypes.c_void_p)
+    for layers, N, ok in ((2, 248, True), (2, 256, False), (1, 256, True)):
+        creates = [("npd_gru_create", lambda out: L.npd_gru_create(N, 512, layers, 1, w,
+                                                                   _rnn_weight_count(3, N, 512, layers, 1), 0, out))]
+        for cell, gates in ((0, 3), (1, 4)):
+            creates.append((f"npd_rnn_create cell {cell}", lambda out, cell=cell, gates=gates: L.npd_rnn_create(
+                cell, N, 512, layers, 1, w, _rnn_weight_count(gates, N, 512, layers, 1), 0, out)))
+        for who, create in creates:
+            out = ctypes.c_void_p(0xdead)
+            rc = create(ctypes.byref(out))
+            if ok:
+                assert rc == 0 and out.value, (who, layers, N, rc, L.npd_last_error())
+                assert L.npd_gru_destroy(out) == 0
+            else:
+                assert rc == -1 and out.value is None, (who, layers, N, rc)
+                assert b"needs N <= 248" in L.npd_last_error() and b"160 KiB" in L.npd_last_error()
 
 
 def test_null_pointer_errors_are_reported_not_fatal():

@@ -1,6 +1,6 @@
 """The conditions on the inputs of the forced-path GPU tests (tests/test_forced_path_gpu.py), on the CPU.
 
-They keep the GPU test from being toothless or unfair, for every row of forced_helper.CASES:
+They keep the GPU test from being toothless or unfair, for every row of forced_helper.CASES and LONG_CASES:
   * E_ref <= bar / 4: the reference's own arithmetic (torch fp32 on the CPU, one net(...) call per step) is within a
     quarter of the bar of float64, on the fully forced path and on its own genie path -- so the bar is one the reference
     passes with room to spare;
@@ -19,7 +19,7 @@ import pytest
 
 import forced_helper as H
 
-BARRED = [c for c in H.CASES if c.bar is not None]
+BARRED = [c for c in H.CASES + H.LONG_CASES if c.bar is not None]
 _cache = {}
 
 
@@ -59,6 +59,50 @@ def test_case_table_reaches_every_decode_instantiation():
         assert {c.rev for c in H.CASES if c.family == f} == {False, True}, f
     assert len({c.id for c in H.CASES}) == len(H.CASES)
     assert set(H.ALTERNATE_LOSS) <= set(H.CASE_BY_ID)
+
+
+def test_long_case_table():
+    """LONG_CASES: N = 256 in every family, lengths that are no power of two, N = 248 at F = 512 x 2 (the LDS exactly
+    full) on both wide kernels, odd K-block counts and the y_h0 route on gru16p_kernel; every case has a bar; both
+    values of onehot and of reverse_order in every family; the route of every case is the family it names; g and the
+    y scale are recorded per case."""
+    assert not set(c.id for c in H.CASES) & set(c.id for c in H.LONG_CASES)
+    assert len({c.id for c in H.LONG_CASES}) == len(H.LONG_CASES) and all(c.ys == 1.0 for c in H.CASES)
+    have = {(c.family, c.F, c.layers, c.precision, c.N, c.yh0) for c in H.LONG_CASES}
+    need = [("gru_decode_kernel", 64, 2, "fp32", 256), ("gru_decode_kernel", 32, 1, "fp32", 256),
+            ("gru_decode_kernel", 64, 1, "fp32", 24), ("gru_decode_bf_kernel", 32, 2, "fp16x3", 256),
+            ("gru_decode_bf_kernel", 32, 2, "bf16x3", 256), ("gru_decode_bf_kernel", 64, 1, "fp16x3", 256),
+            ("gru_decode_bf_kernel", 64, 1, "bf16x3", 256), ("gru_decode_bf_kernel", 32, 1, "fp16x3", 48),
+            ("gru16p_kernel", 64, 2, "fp16x3", 256), ("gru16p_kernel", 64, 2, "bf16x3", 256),
+            ("gru16p_kernel", 64, 2, "fp16x3", 96), ("gru16p_kernel", 64, 2, "fp16x3", 160),
+            ("gru_wide_kernel", 128, 2, "fp32", 256), ("gru_wide_kernel", 512, 1, "fp32", 256),
+            ("gru_wide_kernel", 256, 1, "fp32", 40), ("gru_wide_kernel", 512, 2, "fp32", 248),
+            ("lstm_decode_kernel", 32, 2, "fp32", 256), ("lstm_decode_kernel", 64, 1, "fp32", 256),
+            ("lstm_wide_kernel", 256, 2, "fp32", 256), ("lstm_wide_kernel", 512, 2, "fp32", 248)]
+    for row in need:
+        assert row + (False,) in have, row
+    assert ("gru16p_kernel", 64, 2, "fp16x3", 256, True) in have
+    for c in H.LONG_CASES:
+        assert c.bar == H.bar_of(c.family, c.precision) and c.bar is not None and c.head is None
+        assert c.B == (24 if c.F == 512 else 70) and 8 <= c.N <= 256 and c.N % 8 == 0
+        assert c.g > 0 and (c.ys == 1.0 or (not c.yh0 and np.isclose(c.ys, np.sqrt(16 / c.N))))
+        if c.cell == "LSTM":
+            assert c.precision == "fp32" and c.family == ("lstm_decode_kernel" if c.F * c.layers <= 64 else "lstm_wide_kernel")
+        elif c.precision == "fp32":
+            assert c.family == ("gru_wide_kernel" if c.F > 64 else "gru_decode_kernel")
+        else:
+            assert c.N % 16 == 0
+            assert c.family == ("gru16p_kernel" if c.F == 64 and c.layers == 2 and c.N % 32 == 0 else "gru_decode_bf_kernel")
+        if c.F == 512 and c.layers == 2:  # gru::wide_lds_bytes: all 160 KiB
+            assert (c.layers * c.F + c.N + 8) * 128 == 160 * 1024
+    for f in H.FAMILIES:
+        assert {c.onehot for c in H.LONG_CASES if c.family == f} == {False, True}, f
+        assert {c.rev for c in H.LONG_CASES if c.family == f} == {False, True}, f
+        assert H.LONG_FAMILY_CASE[f].family == f and H.LONG_FAMILY_CASE[f].N == 256
+    for N in (24, 40, 48, 96, 160, 248):  # no code of the reference: a seeded half of the positions
+        info = H.info_set(N)
+        assert info.size == N // 2 and np.array_equal(info, np.unique(info)) and 0 <= info[0] and info[-1] < N
+        assert np.array_equal(info, H.info_set(N))
 
 
 @pytest.mark.parametrize("case", BARRED, ids=lambda c: c.id)

@@ -1,6 +1,7 @@
 """Every RNN decode kernel against float64 along forced paths, on the MI355X (forced_helper.CASES: one case per
 instantiated decode kernel -- gru_decode_kernel, gru_decode_bf_kernel, gru16p_kernel, gru_wide_kernel,
-lstm_decode_kernel, lstm_wide_kernel -- and the y_h0 route of five of them).
+lstm_decode_kernel, lstm_wide_kernel -- and the y_h0 route of five of them; forced_helper.LONG_CASES: every family at
+N = 256, at lengths that are no power of two, and at N = 248 where F = 512 x 2 layers fills the LDS).
 
 Each case runs three decodes through RNN_decoder.decode: A fully forced (gt random +-1, loss_inds []), B genie
 (loss_inds the information set, gt's frozen entries from {-1, +1, 0, -0.3, 2.5}; two cases also with loss_inds = every
@@ -24,6 +25,8 @@ import forced_helper as H
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 _cache = {}
+# one case per family at its smallest length and one at N = 256
+FAMILY_CASES = list(H.FAMILY_CASE.values()) + list(H.LONG_FAMILY_CASE.values())
 
 
 def setup(case):
@@ -49,7 +52,7 @@ def verify(case, sd, y, gt, loss, dec_k, lg_k):
     return H.check_forced(lg_k, dec_k, gt, loss, l64, case.bar, case.rev)
 
 
-@pytest.mark.parametrize("case", H.CASES, ids=lambda c: c.id)
+@pytest.mark.parametrize("case", H.CASES + H.LONG_CASES, ids=lambda c: c.id)
 def test_decode_along_its_own_path(case):
     net, gnet, sd, dec = setup(case)
     errs = {}
@@ -64,11 +67,11 @@ def test_decode_along_its_own_path(case):
             path = H.step_path(dec_k, case.rev)
             e_ref = np.abs(H.ref32_forced(net, case, y, path) - H.f64_forced(case, sd, y, path)).max()
     worst = max(errs.values())
-    print(f"FORCED {case.id} | {case.family} | g {case.g} | bar {case.bar} | max err {worst:.2e} | E_ref {e_ref:.2e} | "
-          f"ratio {worst / e_ref:.2f} | " + " ".join(f"{k} {v:.2e}" for k, v in errs.items()))
+    print(f"FORCED {case.id} | {case.family} | g {case.g} | ys {case.ys:.4f} | bar {case.bar} | max err {worst:.2e} | "
+          f"E_ref {e_ref:.2e} | ratio {worst / e_ref:.2f} | " + " ".join(f"{k} {v:.2e}" for k, v in errs.items()))
 
 
-@pytest.mark.parametrize("case", list(H.FAMILY_CASE.values()), ids=lambda c: c.id)
+@pytest.mark.parametrize("case", FAMILY_CASES, ids=lambda c: c.id)
 def test_negative_control_breaks_the_bar(case):
     """The comparison has teeth end to end: the kernel decodes with weight_hh_l0's last column zeroed (a dropped k element
     of the recurrent product, as weights: the same code on other numbers) and is compared with the UNMUTATED float64
@@ -85,7 +88,7 @@ def test_negative_control_breaks_the_bar(case):
         verify(case, sd, y, gt, loss, dec_k, lg_k)
 
 
-@pytest.mark.parametrize("case", list(H.FAMILY_CASE.values()), ids=lambda c: c.id)
+@pytest.mark.parametrize("case", FAMILY_CASES, ids=lambda c: c.id)
 def test_single_word_batch(case):
     """B = 1: every lane of the tile but one is clamped to row B - 1."""
     net, gnet, sd, dec = setup(case)
@@ -96,7 +99,7 @@ def test_single_word_batch(case):
         verify(case, sd, y, gt, loss, dec_k, lg_k)
 
 
-@pytest.mark.parametrize("case", list(H.FAMILY_CASE.values()), ids=lambda c: c.id)
+@pytest.mark.parametrize("case", FAMILY_CASES, ids=lambda c: c.id)
 def test_rows_past_the_batch_are_untouched(case):
     """npd_gru_decode_ex called directly with decoded / logits the first B = 70 rows of buffers 32 rows longer that hold a
     sentinel bit pattern: the 32 trailing rows of both stay bitwise unchanged, the first B rows are the decode."""

@@ -8,7 +8,13 @@ Bars, all exact (integer counters, +-1 decisions):
   3. the general instantiation (decode_count_sweep with `decoded`), whose decisions are RNN_decoder.decode's.
 Shapes: more than one tile per wave, ragged last tiles, a counter flush at every segment change, reverse order (whose
 trailing steps are all frozen), N = 32 / 64 / 128 (1 / 2 / 4 K blocks of the y projection, K = 16 / 32 / 64 message
-slots), the three split instantiations."""
+slots), the three split instantiations.
+
+Past 64 message columns (test_message_registers_and_slot_255): the message codes of a codeword sit in four registers
+of 64 columns each, and every trained case above has K <= 64, the first register alone.  Seeded nets at (N, K) = (96, 96),
+(160, 160), (256, 200) and (256, 256) reach the second, third and fourth register and message column 255; the count-only
+launch, the general instantiation and the unfused sequence must give the same counters, also after one message column
+at a register boundary is negated."""
 import functools
 
 import numpy as np
@@ -152,3 +158,92 @@ def test_counters_accumulate():
     dec.decode_count_sweep(net, y, msg, c, cols=cols)
     dec.decode_count_sweep(net, y, msg, c, cols=cols)
     assert np.array_equal(c.cpu().numpy(), 2 * sweep_counts("c64_nat"))
+
+
+# ------------------------------------------------------------------------- more than 64 message columns, K = 256
+# name -> (N, K, precision, reverse); K == N: cols is every position, else K random positions, permuted
+LONG = {
+    "n96_k96": (96, 96, "fp16x3", False),
+    "n160_k160": (160, 160, "fp16x3", False),
+    "n256_k200": (256, 200, "fp16x3", False),
+    "n256_k200_rev": (256, 200, "fp16x3", True),
+    "n256_k256": (256, 256, "fp16x3", False),
+    "n256_k256_bf16x3": (256, 256, "bf16x3", False),
+    "n256_k256_bf16": (256, 256, "bf16", False),
+}
+LONG_B = 16 * 9 + 5
+BOUNDARY_COLUMNS = (63, 64, 127, 128, 191, 192)  # and K - 1
+
+
+@functools.lru_cache(maxsize=None)
+def long_setup(name):
+    """(net, decoder, cols, msg (B, K), y (2, B, N)) of a LONG case: a seeded, untrained net (F = 64, 2 layers, one-hot),
+    the decoder's information set a seeded random half of the positions (no code is needed), messages +-1 with some
+    values outside {-1, +1}; built once, never written."""
+    from neural_polar_decoder_amd.rnn import RNN_Model, RNN_decoder
+    N, K, precision, reverse = LONG[name]
+    rng = np.random.default_rng(1000 + N)
+    torch.manual_seed(N)
+    net = RNN_Model("GRU", N + 2, 64, 1, 2, N, 0, 0).to(DEV).eval()
+    info = np.sort(rng.permutation(N)[:N // 2])
+    dec = RNN_decoder("y_input", N, info, onehot=True, reverse_order=reverse, precision=precision)
+    cols = np.arange(N) if K == N else rng.permutation(N)[:K]
+    g = torch.Generator(device="cpu").manual_seed(3 + N)
+    vals = torch.tensor([-1.0, 1.0, -1.0, 1.0, -1.0, 1.0, -1.0, 1.0, 0.0, 2.0, -3.0, 0.4, -0.6])
+    msg = vals[torch.randint(0, len(vals), (LONG_B, K), generator=g)].to(DEV)
+    y = (1.0 - 2.0 * (torch.rand(2, LONG_B, N, generator=g) < 0.5).float() + 0.8 * torch.randn(2, LONG_B, N, generator=g))
+    return net, dec, cols, msg, y.to(DEV).contiguous()
+
+
+@pytest.mark.parametrize("name", list(LONG))
+def test_message_registers_and_slot_255(name):
+    """Exact: the count-only launch == the general instantiation (whose `decoded` is RNN_decoder.decode's) == decode +
+    count_errors(cols=...), for the messages as drawn and, for every k in {63, 64, 127, 128, 191, 192, K - 1} below K,
+    with column k alone negated -- a column that is skipped, or read from another register, changes the count against
+    the unfused one (the negation does change the unfused count: asserted)."""
+    from neural_polar_decoder_amd.utils import count_errors
+    net, dec, cols, msg, y = long_setup(name)
+    K = LONG[name][1]
+    dd = torch.stack([dec.decode(net, False, y[s]) for s in range(2)])
+    frozen = np.setdiff1d(np.arange(dec.N), dec.info_inds)
+    assert bool((dd[:, :, torch.from_numpy(frozen).to(DEV)] == 1.0).all())
+    assert 0.05 < float((dd < 0).float().mean()) < 0.5  # the information positions are not decoded to a constant
+
+    def three_ways(m):
+        ref = torch.zeros(2, 2, dtype=torch.int64, device=DEV)
+        for s in range(2):
+            count_errors(m, dd[s], ref[s], cols=cols)
+        c = torch.zeros(2, 2, dtype=torch.int64, device=DEV)
+        dec.decode_count_sweep(net, y, m, c, cols=cols)
+        out = torch.full_like(y, 7.0)
+        cg = torch.zeros(2, 2, dtype=torch.int64, device=DEV)
+        dec.decode_count_sweep(net, y, m, cg, cols=cols, decoded=out)
+        assert torch.equal(out, dd)
+        return ref.cpu().numpy(), c.cpu().numpy(), cg.cpu().numpy()
+
+    ref0, c0, cg0 = three_ways(msg)
+    print(f"SWEEP {name}: unfused {ref0.tolist()} count-only {c0.tolist()} general {cg0.tolist()}")
+    assert np.array_equal(c0, ref0) and np.array_equal(cg0, ref0), (c0, cg0, ref0)
+    assert (ref0[:, 0] > 0).all() and (ref0[:, 0] < LONG_B * K).all()
+    for k in sorted({k for k in BOUNDARY_COLUMNS + (K - 1,) if k < K}):
+        m = msg.clone()
+        m[:, k] = -m[:, k]
+        ref, c, cg = three_ways(m)
+        print(f"SWEEP {name} column {k} negated: unfused {ref.tolist()} count-only {c.tolist()} general {cg.tolist()}")
+        assert not np.array_equal(ref, ref0), k
+        assert np.array_equal(c, ref) and np.array_equal(cg, ref), (k, c, cg, ref)
+
+
+@pytest.mark.parametrize("with_decoded", [False, True])
+def test_repeat_of_message_255s_position_is_refused(with_decoded):
+    """K = 256: a cols that lists the position of message column 255 twice is refused like any other repeat, before
+    any launch (the counters stay as they were)."""
+    from neural_polar_decoder_amd import _lib
+    net, dec, cols, msg, y = long_setup("n256_k256")
+    for other in (3, 254):
+        bad = cols.copy()
+        bad[other] = bad[255]
+        c = torch.zeros(2, 2, dtype=torch.int64, device=DEV)
+        with pytest.raises(_lib.NpdError, match="repeated column"):
+            dec.decode_count_sweep(net, y, msg, c, cols=bad, decoded=torch.empty_like(y) if with_decoded else None)
+        assert int(c.abs().sum()) == 0

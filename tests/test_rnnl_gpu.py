@@ -122,6 +122,49 @@ def full_words(cand, info, N):
     return w
 
 
+# the longest length the interface takes (N = 256: 256 steps, every word of the path-bit masks in use), K = 128; the
+# exact invariants only -- the tolerance-based ones stay at the shapes above
+LONG_SHAPE = (256, 128, 0, 64, 2, True)
+
+
+def long_setup():
+    """shape_setup's recipe at LONG_SHAPE, 33 words; built once and left unchanged."""
+    if "long" not in _cache:
+        from neural_polar_decoder_amd.montecarlo import seeded_crisp
+        N, K, g, F, layers, onehot = LONG_SHAPE
+        code, info = code_of(N, K, g)
+        net, dec = seeded_crisp(code, F, layers, seed=11, device=DEV, onehot=onehot)
+        with torch.no_grad():
+            for k, p in net.named_parameters():
+                p.mul_(3.0 if k.startswith("rnn.") else 10.0)
+        gen = torch.Generator().manual_seed(5)
+        msg = 1.0 - 2.0 * (torch.rand(33, K, generator=gen) < 0.5).float()
+        y = encode(code, msg.to(DEV)) + 0.7 * torch.randn(33, N, generator=gen).to(DEV)
+        _cache["long"] = (code, info, net, dec, y)
+    return _cache["long"]
+
+
+@pytest.mark.parametrize("L", [1, 4, 8])
+@pytest.mark.parametrize("B", [1, 33])
+def test_longest_length_exact_invariants(B, L):
+    """N = 256, K = 128 on gru_list_kernel.  Invariant 1: L = 1 is the greedy decoder bit for bit, every metric 0 and sel 0;
+    invariant 5: no message repeats within a list (and every survivor is a +-1 word with a finite metric, msg_hat the
+    selected one)."""
+    code, info, net, dec, y_all = long_setup()
+    y = y_all[:B]
+    hat, (cm, ct, sel) = dec.list_decode(net, y, code, L, return_candidates=True)
+    assert cm.shape == (B, L, LONG_SHAPE[1]) and torch.isfinite(ct).all() and (cm.abs() == 1).all()
+    assert torch.equal(hat, cm[torch.arange(B, device=DEV), sel.long()])
+    eq = (cm[:, :, None, :] == cm[:, None, :, :]).all(-1)
+    assert int(eq.sum()) == B * L
+    if L == 1:
+        greedy = dec.decode(net, False, y)[:, torch.as_tensor(info, device=DEV)]
+        assert torch.equal(hat, greedy)
+        assert torch.equal(cm[:, 0], hat) and torch.all(ct == 0) and torch.all(sel == 0)
+        if B > 1:  # over the batch the greedy decode is not a constant
+            assert 0.05 < float((greedy < 0).float().mean()) < 0.95
+
+
 @pytest.mark.parametrize("B", BATCHES)
 @pytest.mark.parametrize("name", list(SHAPES))
 def test_list_size_one_is_the_greedy_decoder(name, B):
