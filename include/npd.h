@@ -445,6 +445,13 @@ int npd_conv_forward(const npd_conv* conv, const float* y, float* logits, float*
  * input4 = layers3(input3) + input3 (models.py:750, :767), channels-first (B, embed/2, N) fp32. */
 int npd_conv_forward_ex(const npd_conv* conv, const float* y, float* logits, float* decoded, float* input4,
                         void* workspace, int64_t B, void* stream);
+/* As npd_conv_forward, and (if tap_out != NULL) one intermediate activation, fp32, in the reference's layout:
+ * tap 0 .. 9: the output of conv layer tap (layers1.0, layers1.2, layers2.0, ..., layers5.2) after GELU and, where the
+ * layer closes a residual block (3, 5, 7), after the residual, channels-first (B, cout, N); tap 10, 11, 12: the
+ * outputs of layersFin.0 / .2 (after GELU) and layersFin.4 (before LayerNorm), (B, 4N), (B, N), (B, N).
+ * npd_conv_forward_ex is tap = 5. */
+int npd_conv_forward_tap(const npd_conv* conv, const float* y, float* logits, float* decoded, int tap, float* tap_out,
+                         void* workspace, int64_t B, void* stream);
 
 #ifdef __cplusplus
 }

@@ -80,6 +80,8 @@ SIGNATURES = [
     ("npd_conv_workspace_bytes", c_i64, [c_void_p, c_i64]),
     ("npd_conv_forward", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
     ("npd_conv_forward_ex", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
+    ("npd_conv_forward_tap", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_i64,
+                                     c_void_p]),
 ]
 
 

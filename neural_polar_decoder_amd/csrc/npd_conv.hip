@@ -712,6 +712,7 @@ static size_t ws16_lds_bytes(int kb, int Q, int dil, int kp) {
 // per MFMA) and the tile lands in LDS with 16-B stores.
 constexpr int GK = 32;
 constexpr int GS = GK + 4;
+constexpr int kFcChain = 32;  // K blocks per accumulation chain of fc_kernel
 
 __global__ __launch_bounds__(256) void fc_kernel(const float* __restrict__ X, const float* __restrict__ Wt,
                                                  const float* __restrict__ bias, float* __restrict__ out, int M, int K,
@@ -745,33 +746,42 @@ __global__ __launch_bounds__(256) void fc_kernel(const float* __restrict__ X, co
             *reinterpret_cast<f4*>(&Bs[buf][r * GS + c4]) = rb[u];
         }
     };
+    // one fp32 accumulation chain covers kFcChain K blocks (1024 terms); the chains' sums are added in tot.  A single
+    // chain over FC0's K = E N terms (up to 65536 here) rounds about sqrt(K) times: 1.3e-7 on O(0.1) outputs at
+    // K = 65536, 14 x a blocked fp32 GEMM's error (tests/conv_layers_helper.py)
     f16v acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    f16v tot = acc;
     const int nk = K / GK;
     fetch(0);
     stash(0);
     __syncthreads();
-    for (int kb = 0; kb < nk; ++kb) {
-        const int cur = kb & 1;
-        if (kb + 1 < nk) fetch((kb + 1) * GK);
-        const f4* as = reinterpret_cast<const f4*>(&As[cur][(msub * 32 + col) * GS + h * (GK / 2)]);
-        const f4* bs = reinterpret_cast<const f4*>(&Bs[cur][(jsub * 32 + col) * GS + h * (GK / 2)]);
+    for (int kb0 = 0; kb0 < nk; kb0 += kFcChain) {
+        const int kend = min(nk, kb0 + kFcChain);
+        for (int kb = kb0; kb < kend; ++kb) {
+            const int cur = kb & 1;
+            if (kb + 1 < nk) fetch((kb + 1) * GK);
+            const f4* as = reinterpret_cast<const f4*>(&As[cur][(msub * 32 + col) * GS + h * (GK / 2)]);
+            const f4* bs = reinterpret_cast<const f4*>(&Bs[cur][(jsub * 32 + col) * GS + h * (GK / 2)]);
 #pragma unroll
-        for (int g = 0; g < GK / 8; ++g) {
-            const f4 a = as[g], b = bs[g];
-            acc = mfma(a.x, b.x, acc);
-            acc = mfma(a.y, b.y, acc);
-            acc = mfma(a.z, b.z, acc);
-            acc = mfma(a.w, b.w, acc);
+            for (int g = 0; g < GK / 8; ++g) {
+                const f4 a = as[g], b = bs[g];
+                acc = mfma(a.x, b.x, acc);
+                acc = mfma(a.y, b.y, acc);
+                acc = mfma(a.z, b.z, acc);
+                acc = mfma(a.w, b.w, acc);
+            }
+            if (kb + 1 < nk) stash(cur ^ 1);
+            __syncthreads();
         }
-        if (kb + 1 < nk) stash(cur ^ 1);
-        __syncthreads();
+        tot += acc;
+        acc = f16v{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     }
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int m = m0 + msub * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
         const int j = j0 + jsub * 32 + col;
         if (m < M) {
-            float v = acc[r] + bias[j];
+            float v = tot[r] + bias[j];
             if (act) v = gelu(v);
             out[(int64_t)m * Nout + j] = v;
         }
@@ -908,6 +918,7 @@ __device__ __forceinline__ void lds_barrier() {
     asm volatile("" ::: "memory");
 }
 constexpr int kWspSlots = 3;
+constexpr int kWspChain = 85;  // ring rounds (of kWspSlots K blocks) per accumulation chain of fc_split_wsp_kernel
 // LDS image of one K block: 64-B rows (32 halfs) with the 16-B chunk q of row r stored at chunk q ^ ((r >> 2) & 3).
 // The MFMA waves' ds_read_b128 (lane -> row col, chunk 2 st + h) then hit all 64 banks in each of its 16-lane groups
 // (rows r and r + 4 of a 256-B bank line differ in the swizzle), and the loaders' stores -- ds_write_b64 of 2 rows x
@@ -1108,8 +1119,45 @@ __global__ __launch_bounds__(512, 1) void fc_split_wsp_kernel(const float* __res
             }
             lds_barrier();
         };
+        // One fp32 accumulation chain covers kWspChain ring rounds (255 K blocks, 8160 terms): a single chain over
+        // FC0's K = E N terms rounds about sqrt(K) times (11 x a blocked fp32 GEMM's error at K = 65536,
+        // tests/conv_layers_helper.py).  A finished chain's sums are parked in this lane's own elements of out (no
+        // registers are free for a second accumulator set at BM = 256) and added back in the epilogue; K <= 8160 never
+        // parks, and both block tiles park at the same K.  Later chains are added with fire-and-forget atomics on
+        // elements only this lane touches, in program order, so the sum is deterministic.
+        auto park = [&](bool add) {
+            // opaque to the optimiser, so that the 16 TM TN addresses are formed here, not kept live across the K loop
+            int lm = wm * 32 * TM + 4 * h, lj = wn * 32 * TN + col;
+            asm volatile("" : "+v"(lm), "+v"(lj));
+#pragma unroll
+            for (int a = 0; a < TM; ++a)
+#pragma unroll
+                for (int b = 0; b < TN; ++b) {
+                    const int j = j0 + lj + 32 * b;
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int m = m0 + lm + 32 * a + (r & 3) + 8 * (r >> 2);
+                        if (m < M) {
+                            float* const p = out + (int64_t)m * Nout + j;
+                            // atomic accesses throughout (the epilogue's load too), so the one location is coherent
+                            // for this lane; the add returns nothing, so nothing waits for a load
+                            if (add) __hip_atomic_fetch_add(p, acc[a][b][r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            else __hip_atomic_store(p, acc[a][b][r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        }
+                        acc[a][b][r] = 0.0f;
+                    }
+                }
+        };
+        bool parked = false;
         int kb = 0;
-        for (; kb + NS <= nk; kb += NS) static_for<0, NS>([&](auto i) { step(i); });
+        for (;;) {
+            int kend = kb + NS * kWspChain;
+            if (nk - kend <= 32) kend = nk;  // a rest of up to 1024 terms joins the last chain
+            for (; kb + NS <= kend; kb += NS) static_for<0, NS>([&](auto i) { step(i); });
+            if (kend == nk) break;
+            park(parked);
+            parked = true;
+        }
         static_for<0, NS>([&](auto i) {
             if (kb + i.value < nk) step(i);
         });
@@ -1124,7 +1172,10 @@ __global__ __launch_bounds__(512, 1) void fc_split_wsp_kernel(const float* __res
                 for (int r = 0; r < 16; ++r) {
                     const int m = m0 + wm * 32 * TM + 32 * a + (r & 3) + 8 * (r >> 2) + 4 * h;
                     if (m < M) {
-                        float v = fmaf(acc[a][b][r], descale, bj);
+                        const float sum = parked ? __hip_atomic_load(out + (int64_t)m * Nout + j, __ATOMIC_RELAXED,
+                                                                     __HIP_MEMORY_SCOPE_AGENT) + acc[a][b][r]
+                                                 : acc[a][b][r];
+                        float v = fmaf(sum, descale, bj);
                         if (act) v = gelu(v);
                         out[(int64_t)m * Nout + j] = v;
                         amx = fmaxf(amx, fabsf(v));
@@ -1452,18 +1503,27 @@ extern "C" int64_t npd_conv_workspace_bytes(const npd_conv* c, int64_t B) {
     return (3 * Bc * (int64_t)c->E * c->N + Bc * 4 * (int64_t)c->N + 2 * Bc * (int64_t)c->N) * 4 + 256 + (int64_t)kAmaxSlots * kAmaxWords * 4;
 }
 
-extern "C" int npd_conv_forward_ex(const npd_conv* c, const float* y, float* logits, float* decoded, float* input4,
-                                   void* workspace, int64_t B, void* stream);
+extern "C" int npd_conv_forward_tap(const npd_conv* c, const float* y, float* logits, float* decoded, int tap,
+                                    float* tap_out, void* workspace, int64_t B, void* stream);
 
 extern "C" int npd_conv_forward(const npd_conv* c, const float* y, float* logits, float* decoded, void* workspace,
                                 int64_t B, void* stream) {
-    return npd_conv_forward_ex(c, y, logits, decoded, nullptr, workspace, B, stream);
+    return npd_conv_forward_tap(c, y, logits, decoded, 5, nullptr, workspace, B, stream);
 }
 
+// input4 is the tap after conv layer 5 (layers3 + residual)
 extern "C" int npd_conv_forward_ex(const npd_conv* c, const float* y, float* logits, float* decoded, float* input4,
                                    void* workspace, int64_t B, void* stream) {
+    return npd_conv_forward_tap(c, y, logits, decoded, 5, input4, workspace, B, stream);
+}
+
+// tap 0 .. 9: conv layer tap's output (after GELU and the residual) as channels-first (B, cout, N); tap 10 .. 12: the
+// FC0 / FC1 / FC2 outputs (B, 4N) / (B, N) / (B, N), FC2 before LayerNorm.  Written only if tap_out != NULL.
+extern "C" int npd_conv_forward_tap(const npd_conv* c, const float* y, float* logits, float* decoded, int tap,
+                                    float* tap_out, void* workspace, int64_t B, void* stream) {
     NPD_ARG(c != nullptr, "npd_conv_forward: conv is NULL");
     NPD_ARG(B >= 0, "npd_conv_forward: B < 0");
+    NPD_ARG(tap >= 0 && tap < kLayers + 3, "npd_conv_forward_tap: tap must be 0 .. 12");
     if (B == 0) return NPD_OK;
     NPD_ARG(y != nullptr && workspace != nullptr, "npd_conv_forward: null pointer");
     NPD_ARG(logits != nullptr || decoded != nullptr, "npd_conv_forward: nothing to write");
@@ -1608,11 +1668,11 @@ extern "C" int npd_conv_forward_ex(const npd_conv* c, const float* y, float* log
             // block (i == 3, 5, 7) is the next block's input and residual
             if (i == 1 || i == 3 || i == 5 || i == 7) res_idx = out_idx;
             in_idx = out_idx;
-            if (i == 5 && input4) {  // input4 = layers3(input3) + residual3 (models.py:750)
+            if (i == tap && tap_out) {  // tap 5: input4 = layers3(input3) + residual3 (models.py:750)
                 dim3 gt((N + 63) / 64, (L.cout + 63) / 64, (unsigned)nb);
-                hipLaunchKernelGGL(act_to_channels_first_kernel, gt, dim3(256), 0, s, o, input4 + b0 * (int64_t)L.cout * N,
-                                   N, L.cout);
-                rc = launch_check("input4 transpose launch");
+                hipLaunchKernelGGL(act_to_channels_first_kernel, gt, dim3(256), 0, s, o,
+                                   tap_out + b0 * (int64_t)L.cout * N, N, L.cout);
+                rc = launch_check("tap transpose launch");
                 if (rc) return rc;
             }
         }
@@ -1666,6 +1726,11 @@ extern "C" int npd_conv_forward_ex(const npd_conv* c, const float* y, float* log
         }
         int rc = launch_check("fc launch");
         if (rc) return rc;
+        if (tap >= kLayers && tap_out) {
+            const int f = tap - kLayers;
+            NPD_HIP(hipMemcpyAsync(tap_out + b0 * (int64_t)fo[f], fout[f], (size_t)nb * fo[f] * 4,
+                                   hipMemcpyDeviceToDevice, s));
+        }
         hipLaunchKernelGGL(layernorm_sign_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, s, H3,
                            c->img + c->off_ln[0], c->img + c->off_ln[1], logits ? logits + b0 * N : nullptr,
                            decoded ? decoded + b0 * N : nullptr, (int)nb, N);

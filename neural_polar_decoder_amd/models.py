@@ -94,7 +94,23 @@ class convNet(nn.Module):
         except Exception:
             pass
 
-    def logits(self, noisy_enc: torch.Tensor, want_decisions=True, want_input4=False):
+    def tap_shape(self, tap: int, B: int):
+        """Shape of activation ``tap`` (npd_conv_forward_tap): conv layers 0 .. 9 channels-first, then FC0 / FC1 / FC2."""
+        n, h, e = self.output_len, self.hidden_dim // 2, self.hidden_dim
+        if not 0 <= tap <= 12:
+            raise ValueError("tap must be 0 .. 12")
+        if tap < 10:
+            return (B, e if tap >= 8 else h, n)
+        return (B, 4 * n if tap == 10 else n)
+
+    def logits(self, noisy_enc: torch.Tensor, want_decisions=True, want_input4=False, tap=None):
+        """(logits, decisions); with ``want_input4`` also the activation after conv layer 5, with ``tap`` = 0 .. 12
+        instead any one intermediate activation (conv layer ``tap``'s output, (B, cout, N); 10, 11, 12: the three
+        Linear outputs, the last before LayerNorm) as a third value."""
+        if tap is not None and want_input4:
+            raise ValueError("ask for input4 or for a tap, not both")
+        if want_input4:
+            tap = 5
         if self.training:
             raise _lib.NpdError("the fused convNet path is inference-only (eval mode)")
         y = _lib.f32c(_lib.stage(noisy_enc, "noisy_enc"))
@@ -107,11 +123,11 @@ class convNet(nn.Module):
         ws = torch.empty(max(int(wsb), 1), dtype=torch.uint8, device=y.device)
         lg = torch.empty(B, self.output_len, dtype=torch.float32, device=y.device)
         dec = torch.empty_like(lg) if want_decisions else None
-        in4 = torch.empty(B, self.hidden_dim // 2, self.output_len, dtype=torch.float32, device=y.device) \
-            if want_input4 else None
-        _lib.check(L.npd_conv_forward_ex(h, _lib.ptr(y), _lib.ptr(lg), _lib.ptr(dec), _lib.ptr(in4), _lib.ptr(ws), B,
-                                         _lib.stream_of(y.device)), "npd_conv_forward")
-        if want_input4:
+        in4 = torch.empty(self.tap_shape(tap, B), dtype=torch.float32, device=y.device) if tap is not None else None
+        _lib.check(L.npd_conv_forward_tap(h, _lib.ptr(y), _lib.ptr(lg), _lib.ptr(dec), 5 if tap is None else int(tap),
+                                          _lib.ptr(in4), _lib.ptr(ws), B, _lib.stream_of(y.device)),
+                   "npd_conv_forward")
+        if tap is not None:
             return _lib.home(lg, noisy_enc), _lib.home(dec, noisy_enc), _lib.home(in4, noisy_enc)
         return _lib.home(lg, noisy_enc), _lib.home(dec, noisy_enc)
 
