@@ -453,6 +453,37 @@ int npd_conv_forward_ex(const npd_conv* conv, const float* y, float* logits, flo
 int npd_conv_forward_tap(const npd_conv* conv, const float* y, float* logits, float* decoded, int tap, float* tap_out,
                          void* workspace, int64_t B, void* stream);
 
+/* ---------------------------------------------------------------------------------- GPT transformer */
+/*
+ * XFormerEndToEndGPT.decode (models.py:398-423; run_models.py:338): at every information position i the whole
+ * post-LN layer stack runs on tokens 0 .. i, each attending to every key <= i (mask row i), and
+ * logit_i = Lin_Decoder(output of token i).  Token 0 = start_embed_layer(y); token j >= 1 = b_{j-1} pos_emb.weight[j],
+ * b = +1 at a frozen position, sign(logit) at an information position.  fp32 throughout, dropout off.
+ * Accepted: embed_dim 64, n_head 8, N = max_len in {16, 32, 64}, 1 <= n_layers <= 8; any information set.
+ * weights: host fp32, the parameters decode reads, each row-major as in the state dict, in this order
+ * (E = 64; n_weights = 192 N + 8449 + 49728 n_layers):
+ *   start_embed_layer.0.weight (E,N), .0.bias (E), .2.weight (E,E), .2.bias (E), .4.weight (E,E), .4.bias (E),
+ *   pos_emb.weight (N,E), Decoder.position_enc_auto.pos_table (N,E) -- the buffer's values, never recomputed --,
+ *   then per layer l of Decoder.layer_stack: slf_attn.w_qs.weight (E,E), w_ks.weight, w_vs.weight, fc.weight,
+ *   slf_attn.layer_norm.weight (E), .bias (E), pos_ffn.w_1.weight (4E,E), w_1.bias (4E), pos_ffn.w_2.weight (E,4E),
+ *   w_2.bias (E), pos_ffn.layer_norm.weight (E), .bias (E),
+ *   then Lin_Decoder.weight (E), Lin_Decoder.bias (1).
+ */
+typedef struct npd_gpt npd_gpt; /* a GPT decoder's weights, repacked for the kernel */
+int npd_gpt_create(int N, int embed_dim, int n_head, int n_layers, const float* weights, int64_t n_weights,
+                   npd_gpt** out);
+/* a NULL handle is an argument error here (NPD_EINVAL), not a no-op */
+int npd_gpt_destroy(npd_gpt* gpt);
+/* scratch memory npd_gpt_decode takes from the caller: 0, the decode lives in LDS and registers (NPD_EINVAL for a
+ * NULL handle or B < 0) */
+int64_t npd_gpt_workspace_bytes(const npd_gpt* gpt, int64_t B);
+/* y (B,N) device; is_info: N bytes of HOST memory, nonzero = information position (read before the call returns);
+ * forced (B,N) device or NULL: token j is built from forced[:, j-1] instead of the decision; decoded (B,N) device:
+ * sign(logit) at information positions (sign(0) = 0), +1 at frozen ones; logits (B,N) device or NULL: 0 at frozen
+ * positions.  One launch on `stream`, no allocation; B = 0 returns NPD_OK. */
+int npd_gpt_decode(const npd_gpt* gpt, const float* y, const uint8_t* is_info, const float* forced, float* decoded,
+                   float* logits, int64_t B, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

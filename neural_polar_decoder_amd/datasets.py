@@ -170,5 +170,21 @@ def convnet_from_checkpoint(ckpt, device="cuda"):
     return net.to(device).eval()
 
 
+def xformer_from_checkpoint(ckpt, device="cuda"):
+    """XFormerEndToEndGPT of a run_models.py checkpoint ({'xformer', 'args'} with --model gpt, the reference's default,
+    run_models.py:125, :717-718).  The state dict loads strictly: the parameters decode never reads are kept."""
+    from .models import XFormerEndToEndGPT
+    if isinstance(ckpt, str):
+        ckpt = load_checkpoint(ckpt)
+    a = ckpt["args"]
+    if getattr(a, "model", "gpt") != "gpt":
+        raise NotImplementedError(f"model {a.model!r}: xformer_from_checkpoint builds the 'gpt' decoder "
+                                  "(convnet_from_checkpoint the 'conv' one)")
+    net = XFormerEndToEndGPT(a)
+    net.load_state_dict(ckpt["xformer"], strict=True)
+    return net.to(device).eval()
+
+
 __all__ = ["polar_test_path", "pac_test_path", "load_standard", "make_standard", "save_standard",
-           "evaluate_standard", "load_checkpoint", "code_from_args", "rnn_from_checkpoint", "convnet_from_checkpoint"]
+           "evaluate_standard", "load_checkpoint", "code_from_args", "rnn_from_checkpoint", "convnet_from_checkpoint",
+           "xformer_from_checkpoint"]

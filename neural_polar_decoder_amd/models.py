@@ -4,6 +4,9 @@ Same modules and parameter names as the reference (so ``load_state_dict`` of a r
 works); ``decode``/``forward`` run the whole network through libnpd's MFMA kernels
 (npd_conv_forward): implicit-GEMM dilated Conv1d + GELU (+ residual) layers, FC GEMMs with fused
 bias/GELU, LayerNorm + sign.
+
+XFormerEndToEndGPT -- drop-in for models.XFormerEndToEndGPT (models.py:340-423, ``--model gpt``): the same module
+tree; ``decode`` runs the successive decode in one launch of npd_gpt_decode.
 """
 from __future__ import annotations
 
@@ -143,3 +146,269 @@ class convNet(nn.Module):
         """models.py:769-772: (decoded_msg_bits (B,N,1), mask)."""
         _, dec = self.logits(noisy_enc)
         return dec.unsqueeze(-1), mask
+
+
+# ------------------------------------------------------------------------------------ GPT transformer
+def _sinusoid_table(n_position: int, d_hid: int, num: float = 10000.0) -> torch.Tensor:
+    """(1, n_position, d_hid) fp32: sin at even, cos at odd features of pos / num^(2 (j // 2) / d_hid), from float64."""
+    pos = np.arange(n_position, dtype=np.float64)[:, None]
+    j = np.arange(d_hid)
+    ang = pos / np.power(num, 2 * (j // 2) / d_hid)[None, :]
+    ang[:, 0::2] = np.sin(ang[:, 0::2])
+    ang[:, 1::2] = np.cos(ang[:, 1::2])
+    return torch.FloatTensor(ang).unsqueeze(0)
+
+
+class ScalarMult(nn.Module):
+    """A learnt scalar the reference declares and never applies (kept so that its state dicts load strictly)."""
+
+    def __init__(self):
+        super().__init__()
+        self.alpha = nn.Parameter(1e-10 * torch.ones(1))
+
+    def forward(self, x):
+        return self.alpha * x
+
+
+class ScaledDotProductAttention(nn.Module):
+    def __init__(self, temperature, attn_dropout=0.1):
+        super().__init__()
+        self.temperature = temperature
+        self.dropout = nn.Dropout(attn_dropout)
+
+    def forward(self, q, k, v, mask=None):
+        attn = torch.matmul(q / self.temperature, k.transpose(2, 3))
+        if mask is not None:
+            attn = attn.masked_fill(mask == 0, -1e9)
+        attn = self.dropout(torch.softmax(attn, dim=-1))
+        return torch.matmul(attn, v), attn
+
+
+class MultiHeadAttention(nn.Module):
+    """Post-LN self-attention block: bias-free projections, residual, LayerNorm(eps 1e-6)."""
+
+    def __init__(self, n_head, d_model, d_k, d_v, dropout=0.1):
+        super().__init__()
+        self.n_head, self.d_k, self.d_v = n_head, d_k, d_v
+        self.w_qs = nn.Linear(d_model, n_head * d_k, bias=False)
+        self.w_ks = nn.Linear(d_model, n_head * d_k, bias=False)
+        self.w_vs = nn.Linear(d_model, n_head * d_v, bias=False)
+        self.fc = nn.Linear(n_head * d_v, d_model, bias=False)
+        self.attention = ScaledDotProductAttention(temperature=d_k ** 0.5)
+        self.dropout = nn.Dropout(dropout)
+        self.layer_norm = nn.LayerNorm(d_model, eps=1e-6)
+        self.scalar = ScalarMult()
+
+    def forward(self, q, k, v, mask=None):
+        B, lq, lk = q.size(0), q.size(1), k.size(1)
+        residual = q
+        q = self.w_qs(q).view(B, lq, self.n_head, self.d_k).transpose(1, 2)
+        k = self.w_ks(k).view(B, lk, self.n_head, self.d_k).transpose(1, 2)
+        v = self.w_vs(v).view(B, lk, self.n_head, self.d_v).transpose(1, 2)
+        if mask is not None:
+            mask = mask.unsqueeze(1)
+        o, attn = self.attention(q, k, v, mask=mask)
+        o = self.dropout(self.fc(o.transpose(1, 2).contiguous().view(B, lq, -1)))
+        return self.layer_norm(o + residual), attn
+
+
+class PositionwiseFeedForward(nn.Module):
+    def __init__(self, d_in, d_hid, dropout=0.1):
+        super().__init__()
+        self.w_1 = nn.Linear(d_in, d_hid)
+        self.w_2 = nn.Linear(d_hid, d_in)
+        self.layer_norm = nn.LayerNorm(d_in, eps=1e-6)
+        self.dropout = nn.Dropout(dropout)
+        self.scalar = ScalarMult()
+
+    def forward(self, x):
+        return self.layer_norm(self.dropout(self.w_2(torch.nn.functional.gelu(self.w_1(x)))) + x)
+
+
+class EncoderLayer(nn.Module):
+    def __init__(self, d_model, d_inner, n_head, d_k, d_v, dropout=0.1):
+        super().__init__()
+        self.slf_attn = MultiHeadAttention(n_head, d_model, d_k, d_v, dropout=dropout)
+        self.pos_ffn = PositionwiseFeedForward(d_model, d_inner, dropout=dropout)
+
+    def forward(self, x, slf_attn_mask=None):
+        x, attn = self.slf_attn(x, x, x, mask=slf_attn_mask)
+        return self.pos_ffn(x), attn
+
+
+class PositionalEncoding(nn.Module):
+    def __init__(self, d_hid, n_position=200, num=10000):
+        super().__init__()
+        self.register_buffer("pos_table", _sinusoid_table(n_position, d_hid, num))
+
+    def forward(self, x):
+        return x + self.pos_table[:, :x.size(1)].clone().detach()
+
+
+class XFormerGPT(nn.Module):
+    """The layer stack (models.py:299-336); layer_norm and layer_norm_cross exist and are never applied."""
+
+    def __init__(self, config):
+        super().__init__()
+        self.embed_dim = config.embed_dim
+        self.block_len = config.max_len
+        self.position_enc_auto = PositionalEncoding(self.embed_dim, n_position=self.block_len)
+        self.dropout = nn.Dropout(p=config.dropout)
+        d = config.embed_dim // config.n_head
+        self.layer_stack = nn.ModuleList([EncoderLayer(config.embed_dim, config.embed_dim * 4, config.n_head, d, d,
+                                                       dropout=config.dropout) for _ in range(config.n_layers)])
+        self.layer_norm = nn.LayerNorm(config.embed_dim, eps=1e-6)
+        self.layer_norm_cross = nn.LayerNorm(config.embed_dim, eps=1e-6)
+
+    def forward(self, trg_seq, trg_mask, device=None):
+        x = self.dropout(self.position_enc_auto(trg_seq))
+        for layer in self.layer_stack:
+            x, _ = layer(x, slf_attn_mask=trg_mask)
+        return x
+
+
+class XFormerEndToEndGPT(nn.Module):
+    """Drop-in for models.XFormerEndToEndGPT (models.py:340-423), the reference's default ``--model gpt``.
+
+    ``decode`` / ``decode_logits`` run the whole successive decode in one launch of libnpd's fused kernel
+    (npd_gpt_decode): at every information position the layer stack runs on the prefix built so far, every token
+    attending to every key up to that position.  ``forward`` (teacher-forced, causal; the training-time API) is plain
+    torch.  The kernel covers embed_dim 64, n_head 8, N = max_len in {16, 32, 64}, 1 .. 8 layers
+    (:meth:`fused_supported`); anything else raises NpdError -- there is no eager fall-back."""
+
+    def __init__(self, config):
+        super().__init__()
+        self.embed_dim = config.embed_dim
+        self.block_len = config.max_len
+        self.N = config.N
+        self.n_head = config.n_head
+        self.n_layers = config.n_layers
+        self.trg_pad_idx = 2
+        e = self.embed_dim
+        self.start_embed_layer = nn.Sequential(nn.Linear(config.N, e), nn.GELU(), nn.Linear(e, e), nn.GELU(),
+                                               nn.Linear(e, e))
+        self.learnt_pos = True
+        self.pos_emb = nn.Embedding(self.block_len, e)
+        self.layer_norm_inp = nn.LayerNorm(e, eps=1e-6)
+        self.layer_norm_out = nn.LayerNorm(e, eps=1e-6)
+        self.Decoder = XFormerGPT(config)
+        self.Lin_Decoder = nn.Linear(e, 1)
+        self._handle = None
+        self._hkey = None
+
+    # ------------------------------------------------------------------ teacher-forced forward (plain torch)
+    def forward(self, noisy_enc, mask, trg_seq, device):
+        """models.py:365-396: (output (B,N,2), decoded_msg_bits (B,N,1), mask, logits (B,N,1)); token j is built from
+        trg_seq[:, j-1], attention is causal."""
+        B = trg_seq.size(0)
+        seq = torch.cat((torch.ones((B, 1), device=device), trg_seq[:, :-1]), -1)
+        L = seq.size(1)
+        causal = torch.tril(torch.ones((1, L, L), device=device)).bool()
+        trg_mask = (seq != self.trg_pad_idx).unsqueeze(-2) & causal
+        tok = seq.unsqueeze(-1) * self.pos_emb(torch.arange(self.block_len, device=device))
+        tok = torch.cat((self.start_embed_layer(noisy_enc).unsqueeze(1), tok[:, 1:]), 1)
+        logits = self.Lin_Decoder(self.Decoder(tok, trg_mask, device))
+        out = torch.sigmoid(logits)
+        return torch.cat((1 - out, out), -1), logits.sign(), mask, logits
+
+    # ------------------------------------------------------------------ fused path
+    def fused_reason(self) -> str:
+        """Why the fused kernel does not cover this configuration ('' if it does)."""
+        if self.embed_dim != 64:
+            return f"embed_dim {self.embed_dim}: the fused GPT kernel is built for embed_dim 64"
+        if self.n_head != 8:
+            return f"n_head {self.n_head}: the fused GPT kernel is built for 8 heads"
+        if self.block_len != self.N:
+            return f"max_len {self.block_len} != N {self.N}: the fused GPT kernel needs max_len == N"
+        if self.N not in (16, 32, 64):
+            return f"N {self.N}: the fused GPT kernel covers N in (16, 32, 64)"
+        if not 1 <= self.n_layers <= 8:
+            return f"n_layers {self.n_layers}: the fused GPT kernel covers 1 .. 8 layers"
+        return ""
+
+    def fused_supported(self) -> bool:
+        return self.fused_reason() == ""
+
+    def _packed(self) -> np.ndarray:
+        """The weights npd_gpt_create reads, in the order include/npd.h documents."""
+        def a(t):
+            return t.detach().float().cpu().numpy().ravel()
+        parts = []
+        for li in (0, 2, 4):
+            parts += [a(self.start_embed_layer[li].weight), a(self.start_embed_layer[li].bias)]
+        parts += [a(self.pos_emb.weight), a(self.Decoder.position_enc_auto.pos_table[0, :self.N])]
+        for layer in self.Decoder.layer_stack:
+            at, ff = layer.slf_attn, layer.pos_ffn
+            parts += [a(at.w_qs.weight), a(at.w_ks.weight), a(at.w_vs.weight), a(at.fc.weight),
+                      a(at.layer_norm.weight), a(at.layer_norm.bias), a(ff.w_1.weight), a(ff.w_1.bias),
+                      a(ff.w_2.weight), a(ff.w_2.bias), a(ff.layer_norm.weight), a(ff.layer_norm.bias)]
+        parts += [a(self.Lin_Decoder.weight), a(self.Lin_Decoder.bias)]
+        return np.ascontiguousarray(np.concatenate(parts), dtype=np.float32)
+
+    def _get_handle(self, device):
+        tensors = list(self.parameters()) + [self.Decoder.position_enc_auto.pos_table]
+        key = (str(device), tuple(p._version for p in tensors), tuple(p.data_ptr() for p in tensors))
+        if self._handle is None or self._hkey != key:
+            W = self._packed()
+            out = ctypes.c_void_p()
+            L = _lib.load()
+            with torch.cuda.device(device):
+                _lib.check(L.npd_gpt_create(int(self.N), int(self.embed_dim), int(self.n_head), int(self.n_layers),
+                                            W.ctypes.data_as(ctypes.c_void_p), int(W.size), ctypes.byref(out)),
+                           "npd_gpt_create")
+            if self._handle is not None:
+                L.npd_gpt_destroy(self._handle)
+            self._handle, self._hkey = out, key
+        return self._handle
+
+    def __del__(self):
+        try:
+            if self._handle is not None:
+                _lib.load().npd_gpt_destroy(self._handle)
+        except Exception:
+            pass
+
+    def _is_info(self, info_positions) -> np.ndarray:
+        info = np.asarray(info_positions.cpu() if isinstance(info_positions, torch.Tensor) else info_positions)
+        info = info.astype(np.int64).ravel()
+        if info.size and (info.min() < 0 or info.max() >= self.N):
+            raise ValueError("info_positions must lie in 0 .. N - 1")
+        m = np.zeros(self.N, dtype=np.uint8)
+        m[info] = 1
+        return m
+
+    def decode_logits(self, y, info_positions, forced=None):
+        """(bits (B,N), logits (B,N)) of the successive decode; logits are 0 and bits +1 at frozen positions.  With
+        ``forced`` (B,N) of +-1, token j is built from forced[:, j-1] instead of the decision (the bits returned are
+        still the signs of the logits)."""
+        reason = self.fused_reason()
+        if reason:
+            raise _lib.NpdError(reason)
+        if self.training:
+            raise _lib.NpdError("the fused GPT path is inference-only (eval mode)")
+        if y.dim() != 2 or y.shape[1] != self.N:
+            raise ValueError("input must be (B, N) with N = config.N")
+        is_info = self._is_info(info_positions)
+        yd = _lib.f32c(_lib.stage(y, "noisy_enc"))
+        B = yd.shape[0]
+        fd = None
+        if forced is not None:
+            if tuple(forced.shape) != (B, self.N):
+                raise ValueError("forced must be (B, N)")
+            fd = _lib.f32c(_lib.stage(forced, "forced", yd.device))
+        h = self._get_handle(yd.device)
+        bits = torch.empty(B, self.N, dtype=torch.float32, device=yd.device)
+        lg = torch.empty_like(bits)
+        L = _lib.load()
+        with torch.cuda.device(yd.device):
+            _lib.check(L.npd_gpt_decode(h, _lib.ptr(yd), is_info.ctypes.data_as(ctypes.c_void_p), _lib.ptr(fd),
+                                        _lib.ptr(bits), _lib.ptr(lg), B, _lib.stream_of(yd.device)), "npd_gpt_decode")
+        return _lib.home(bits, y), _lib.home(lg, y)
+
+    def decode(self, noisy_enc, info_positions, mask, device):
+        """models.py:398-423: (output_bits (B,N), mask).  Every test-time caller passes an all-ones mask
+        (run_models.py:326); anything else is refused."""
+        if mask is not None and not bool(torch.as_tensor(mask).all()):
+            raise _lib.NpdError("the fused GPT decode takes an all-ones mask (run_models.py:326)")
+        bits, _ = self.decode_logits(noisy_enc, info_positions)
+        return bits, mask

@@ -321,6 +321,30 @@ class ConvMonteCarlo(DecoderMonteCarlo):
         return self.net.logits(y)[1]
 
 
+class GPTMonteCarlo(DecoderMonteCarlo):
+    """GPT transformer decoding (run_models.py:338-346, testXformer with the default --model gpt): the successive
+    decode's bits at the info positions vs the message."""
+
+    def __init__(self, code, net, snrs, total_cw, batch, seed=1234, rank=None, world=None, device=None):
+        super().__init__(code, snrs, total_cw, batch, seed, rank, world, device)
+        if not net.fused_supported():
+            from ._lib import NpdError
+            raise NpdError(net.fused_reason())
+        self.net = net
+
+    def decisions(self, y):
+        return self.net.decode_logits(y, self.info_np)[0]
+
+
+def seeded_gpt(N, n_layers=6, seed=0, device="cuda"):
+    """XFormerEndToEndGPT (models.py:340-423; embed_dim 64, 8 heads, the reference's defaults) with
+    PyTorch-default-initialised weights under torch.manual_seed(seed)."""
+    from .models import XFormerEndToEndGPT
+    torch.manual_seed(seed)
+    cfg = argparse.Namespace(embed_dim=64, max_len=N, N=N, n_head=8, n_layers=n_layers, dropout=0.0, model="gpt")
+    return XFormerEndToEndGPT(cfg).to(device).eval()
+
+
 def seeded_crisp(code, feature_size=64, depth=2, seed=0, device="cuda", onehot=True, precision="fp32"):
     """(net, RNN_decoder) with PyTorch-default-initialised weights under torch.manual_seed(seed): the
     reference ships no trained checkpoint (rnn_all.py:294-398 architecture, y_input + onehot)."""
@@ -344,7 +368,7 @@ def seeded_conv(N, embed_dim=128, seed=0, device="cuda"):
 
 def _parse_args(argv=None):
     ap = argparse.ArgumentParser(description="MI355X BER/BLER Monte-Carlo (SC, SC-List, exact-LSE SC, ML, bitwise MAP, "
-                                             "CRISP GRU, CRISP GRU list, convNet decoders)")
+                                             "CRISP GRU, CRISP GRU list, convNet, GPT transformer decoders)")
     ap.add_argument("--code", choices=["polar", "pac"], default="polar")
     ap.add_argument("--N", type=int, default=64)
     ap.add_argument("--K", type=int, default=32)
@@ -378,6 +402,11 @@ def _parse_args(argv=None):
     ap.add_argument("--conv", action="store_true", help="also run the convNet decoder (run_models.py:333)")
     ap.add_argument("--conv_checkpoint", default=None, help="run_models.py checkpoint ({'xformer', 'args'}) for --conv")
     ap.add_argument("--embed_dim", type=int, default=128, help="--conv without checkpoint: channels")
+    ap.add_argument("--gpt", action="store_true", help="also run the GPT transformer decoder (run_models.py:338, "
+                                                       "--model gpt; N in 16, 32, 64)")
+    ap.add_argument("--gpt_checkpoint", default=None, help="run_models.py checkpoint ({'xformer', 'args'}, model gpt) "
+                                                           "for --gpt")
+    ap.add_argument("--gpt_layers", type=int, default=6, help="--gpt without checkpoint: transformer layers (1 .. 8)")
     ap.add_argument("--init_seed", type=int, default=0, help="torch seed of the untrained (seeded) decoder weights")
     a = ap.parse_args(argv)
     if a.crc_len is not None:
@@ -466,6 +495,18 @@ def _main(argv=None):
         else:
             cnet = seeded_conv(a.N, a.embed_dim, a.init_seed)
         conv = ConvMonteCarlo(code, cnet, snrs, a.test_size, a.batch_size, a.seed).run()
+    gpt = None
+    if a.gpt:
+        if a.gpt_checkpoint:
+            from .datasets import xformer_from_checkpoint
+            gnet = xformer_from_checkpoint(a.gpt_checkpoint)
+            if gnet.N != a.N:
+                raise SystemExit("--gpt_checkpoint was trained for a different N")
+        else:
+            gnet = seeded_gpt(a.N, a.gpt_layers, a.init_seed)
+        if not gnet.fused_supported():
+            raise SystemExit("--gpt: " + gnet.fused_reason())
+        gpt = GPTMonteCarlo(code, gnet, snrs, a.test_size, a.batch_size, a.seed).run()
     if _dist() is None or _dist().get_rank() == 0:
         print("Test SNRs : ", snrs)
         if crisp is not None:
@@ -505,6 +546,10 @@ def _main(argv=None):
         if conv is not None:
             print("BLERs of Xformer: {0}".format(conv.bler))
             rec["conv"] = conv.as_dict()
+        if gpt is not None:
+            print("BERs of GPT Xformer: {0}".format(gpt.ber))
+            print("BLERs of GPT Xformer: {0}".format(gpt.bler))
+            rec["gpt"] = dict(gpt.as_dict(), n_layers=gnet.n_layers)
         print(json.dumps(rec))
     return res
 
