@@ -484,6 +484,57 @@ int64_t npd_gpt_workspace_bytes(const npd_gpt* gpt, int64_t B);
 int npd_gpt_decode(const npd_gpt* gpt, const float* y, const uint8_t* is_info, const float* forced, float* decoded,
                    float* logits, int64_t B, void* stream);
 
+/* ------------------------------------------------------------------- encoder / decoder transformer models */
+/*
+ * XFormerEndToEndDecoder.decode (models.py:635-654; --model decoder), with the attention mask applied to the keys of
+ * every word (the masking branch under which the reference runs at any batch size).  Once per word the memory
+ * Mem[j] = LN_cross(y_j emb_cross.weight[j+1] + position_enc_cross.pos_table[j]).  At every information position i
+ * the layer stack runs on the tokens D[t] = LN(emb_inputs.weight[idx_t] + position_enc_auto.pos_table[t]), t = 0 .. i
+ * (idx_0 = 2; idx_t = 1 if the bit at position t-1 is +1, else 0; a frozen position's bit is +1): per layer
+ * self-attention over the keys <= i, cross-attention over all N rows of Mem, the FFN; logit_i = Lin_Decoder(token i).
+ * Accepted: embed_dim 64, n_head 8, N = max_len in {16, 32, 64}, 1 <= n_layers <= 8; any information set.
+ * weights: host fp32, each row-major as in the state dict, in this order (E = 64;
+ * n_weights = 192 N + 641 + 66240 n_layers):
+ *   Decoder.emb_cross.weight (N+1,E), Decoder.position_enc_cross.pos_table (N,E), Decoder.layer_norm_cross.weight (E),
+ *   .bias (E), Decoder.emb_inputs.weight (4,E), Decoder.position_enc_auto.pos_table (N,E), Decoder.layer_norm.weight
+ *   (E), .bias (E),
+ *   then per layer l of Decoder.layer_stack: slf_attn.w_qs.weight (E,E), w_ks.weight, w_vs.weight, fc.weight,
+ *   slf_attn.layer_norm.weight (E), .bias (E), the same six of enc_attn, pos_ffn.w_1.weight (4E,E), w_1.bias (4E),
+ *   pos_ffn.w_2.weight (E,4E), w_2.bias (E), pos_ffn.layer_norm.weight (E), .bias (E),
+ *   then Lin_Decoder.weight (E), Lin_Decoder.bias (1).
+ * Both sinusoid tables are the buffers' values, never recomputed.
+ */
+typedef struct npd_xfdec npd_xfdec; /* a decoder model's weights, repacked for the kernel */
+int npd_xfdec_create(int N, int embed_dim, int n_head, int n_layers, const float* weights, int64_t n_weights,
+                     npd_xfdec** out);
+/* a NULL handle is an argument error here (NPD_EINVAL), not a no-op */
+int npd_xfdec_destroy(npd_xfdec* dec);
+/* scratch memory npd_xfdec_decode takes from the caller: 0 (NPD_EINVAL for a NULL handle or B < 0) */
+int64_t npd_xfdec_workspace_bytes(const npd_xfdec* dec, int64_t B);
+/* the operands of npd_gpt_decode: y (B,N) device; is_info: N bytes of HOST memory; forced (B,N) device of +-1 or NULL:
+ * token j is built from forced[:, j-1] instead of the decision; decoded (B,N) device; logits (B,N) device or NULL:
+ * 0 at frozen positions.  One launch on `stream`, no allocation; B = 0 returns NPD_OK. */
+int npd_xfdec_decode(const npd_xfdec* dec, const float* y, const uint8_t* is_info, const float* forced, float* decoded,
+                     float* logits, int64_t B, void* stream);
+
+/*
+ * XFormerEndToEndEncoder.forward / decode (models.py:671-686; --model encoder) with an all-ones mask: one pass,
+ * X[j] = LN(y_j Encoder.pos_emb.weight[j+1] + Encoder.position_enc.pos_table[j]), n_layers encoder layers with full
+ * attention over the N tokens, logit[j] = Lin_Decoder(X[j]) for every j.  Accepted shapes as above.
+ * weights, in this order (n_weights = 128 N + 257 + 49728 n_layers):
+ *   Encoder.pos_emb.weight (N+1,E), Encoder.position_enc.pos_table (N,E), Encoder.layer_norm.weight (E), .bias (E),
+ *   then per layer of Encoder.layer_stack the twelve tensors npd_gpt_create reads per layer,
+ *   then Lin_Decoder.weight (E), Lin_Decoder.bias (1).
+ */
+typedef struct npd_xfenc npd_xfenc; /* an encoder model's weights, repacked for the kernel */
+int npd_xfenc_create(int N, int embed_dim, int n_head, int n_layers, const float* weights, int64_t n_weights,
+                     npd_xfenc** out);
+int npd_xfenc_destroy(npd_xfenc* enc);                               /* NULL handle: NPD_EINVAL */
+int64_t npd_xfenc_workspace_bytes(const npd_xfenc* enc, int64_t B); /* 0; NULL handle or B < 0: NPD_EINVAL */
+/* y (B,N) device; bits (B,N) device: sign(logit) at every position (sign(0) = 0); logits (B,N) device or NULL.
+ * One launch on `stream`, no allocation; B = 0 returns NPD_OK. */
+int npd_xfenc_forward(const npd_xfenc* enc, const float* y, float* bits, float* logits, int64_t B, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

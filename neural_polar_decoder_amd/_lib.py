@@ -86,6 +86,14 @@ SIGNATURES = [
     ("npd_gpt_destroy", c_int, [c_void_p]),
     ("npd_gpt_workspace_bytes", c_i64, [c_void_p, c_i64]),
     ("npd_gpt_decode", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
+    ("npd_xfdec_create", c_int, [c_int, c_int, c_int, c_int, c_void_p, c_i64, ctypes.POINTER(c_void_p)]),
+    ("npd_xfdec_destroy", c_int, [c_void_p]),
+    ("npd_xfdec_workspace_bytes", c_i64, [c_void_p, c_i64]),
+    ("npd_xfdec_decode", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
+    ("npd_xfenc_create", c_int, [c_int, c_int, c_int, c_int, c_void_p, c_i64, ctypes.POINTER(c_void_p)]),
+    ("npd_xfenc_destroy", c_int, [c_void_p]),
+    ("npd_xfenc_workspace_bytes", c_i64, [c_void_p, c_i64]),
+    ("npd_xfenc_forward", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
 ]
 
 

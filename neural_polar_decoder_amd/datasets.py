@@ -171,16 +171,20 @@ def convnet_from_checkpoint(ckpt, device="cuda"):
 
 
 def xformer_from_checkpoint(ckpt, device="cuda"):
-    """XFormerEndToEndGPT of a run_models.py checkpoint ({'xformer', 'args'} with --model gpt, the reference's default,
-    run_models.py:125, :717-718).  The state dict loads strictly: the parameters decode never reads are kept."""
-    from .models import XFormerEndToEndGPT
+    """The transformer of a run_models.py checkpoint ({'xformer', 'args'}): XFormerEndToEndGPT for --model gpt (the
+    reference's default, run_models.py:125, :717-718), XFormerEndToEndEncoder / XFormerEndToEndDecoder for --model
+    encoder / decoder (run_models.py:719-722).  The state dict loads strictly: the parameters decode never reads are
+    kept."""
+    from .models import XFormerEndToEndDecoder, XFormerEndToEndEncoder, XFormerEndToEndGPT
     if isinstance(ckpt, str):
         ckpt = load_checkpoint(ckpt)
     a = ckpt["args"]
-    if getattr(a, "model", "gpt") != "gpt":
-        raise NotImplementedError(f"model {a.model!r}: xformer_from_checkpoint builds the 'gpt' decoder "
-                                  "(convnet_from_checkpoint the 'conv' one)")
-    net = XFormerEndToEndGPT(a)
+    classes = {"gpt": XFormerEndToEndGPT, "encoder": XFormerEndToEndEncoder, "decoder": XFormerEndToEndDecoder}
+    model = getattr(a, "model", "gpt")
+    if model not in classes:
+        raise NotImplementedError(f"model {model!r}: xformer_from_checkpoint builds the 'gpt', 'encoder' and 'decoder' "
+                                  "transformers (convnet_from_checkpoint the 'conv' one)")
+    net = classes[model](a)
     net.load_state_dict(ckpt["xformer"], strict=True)
     return net.to(device).eval()
 

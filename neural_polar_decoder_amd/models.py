@@ -7,6 +7,9 @@ bias/GELU, LayerNorm + sign.
 
 XFormerEndToEndGPT -- drop-in for models.XFormerEndToEndGPT (models.py:340-423, ``--model gpt``): the same module
 tree; ``decode`` runs the successive decode in one launch of npd_gpt_decode.
+
+XFormerEndToEndDecoder / XFormerEndToEndEncoder -- drop-ins for the reference's ``--model decoder`` (models.py:599-654)
+and ``--model encoder`` (models.py:662-686): ``decode`` runs in one launch of npd_xfdec_decode / npd_xfenc_forward.
 """
 from __future__ import annotations
 
@@ -410,5 +413,295 @@ class XFormerEndToEndGPT(nn.Module):
         (run_models.py:326); anything else is refused."""
         if mask is not None and not bool(torch.as_tensor(mask).all()):
             raise _lib.NpdError("the fused GPT decode takes an all-ones mask (run_models.py:326)")
+        bits, _ = self.decode_logits(noisy_enc, info_positions)
+        return bits, mask
+
+
+# ------------------------------------------------------------------- encoder / decoder transformer models
+class DecoderLayer(nn.Module):
+    """Self-attention, cross-attention over the memory, FFN (models.py:178-197)."""
+
+    def __init__(self, d_model, d_inner, n_head, d_k, d_v, dropout=0.1):
+        super().__init__()
+        self.slf_attn = MultiHeadAttention(n_head, d_model, d_k, d_v, dropout=dropout)
+        self.enc_attn = MultiHeadAttention(n_head, d_model, d_k, d_v, dropout=dropout)
+        self.pos_ffn = PositionwiseFeedForward(d_model, d_inner, dropout=dropout)
+
+    def forward(self, x, mem, slf_attn_mask=None, dec_enc_attn_mask=None):
+        x, slf = self.slf_attn(x, x, x, mask=slf_attn_mask)
+        x, cross = self.enc_attn(x, mem, mem, mask=dec_enc_attn_mask)
+        return self.pos_ffn(x), slf, cross
+
+
+def _key_mask(mask):
+    """A (b, L) mask over the keys of each word, in the (b, 1, L) form MultiHeadAttention broadcasts over heads and
+    queries -- the reference's masking branch for these two models."""
+    return None if mask is None else mask.unsqueeze(1)
+
+
+class XFormerEncoder(nn.Module):
+    """models.py:223-250: token j = LayerNorm(y_j pos_emb[j+1] + table[j]), then the encoder layers."""
+
+    def __init__(self, config):
+        super().__init__()
+        self.embed_dim = config.embed_dim
+        self.block_len = config.max_len
+        self.pos_emb = nn.Embedding(config.N + 1, config.embed_dim, padding_idx=0)
+        self.position_enc = PositionalEncoding(self.embed_dim, n_position=self.block_len)
+        self.dropout = nn.Dropout(p=config.dropout)
+        d = config.embed_dim // config.n_head
+        self.layer_stack = nn.ModuleList([EncoderLayer(config.embed_dim, config.embed_dim * 4, config.n_head, d, d,
+                                                       dropout=config.dropout) for _ in range(config.n_layers)])
+        self.layer_norm = nn.LayerNorm(config.embed_dim, eps=1e-6)
+
+    def forward(self, noisy_enc, src_mask, device):
+        """noisy_enc (b, L, E): y repeated over the features; src_mask (b, L) over the keys."""
+        x = noisy_enc * self.pos_emb(torch.arange(1, self.block_len + 1, device=device))
+        x = self.layer_norm(self.dropout(self.position_enc(x)))
+        for layer in self.layer_stack:
+            x, _ = layer(x, slf_attn_mask=_key_mask(src_mask))
+        return x
+
+
+class XFormerDecoder(nn.Module):
+    """models.py:252-297: the memory is LayerNorm_cross(y_j emb_cross[j+1] + table_5000[j]) (no encoder stack), the
+    tokens LayerNorm(emb_inputs[idx_t] + table_10000[t]); every layer cross-attends.  emb_auto is never read."""
+
+    def __init__(self, config):
+        super().__init__()
+        self.embed_dim = config.embed_dim
+        self.block_len = config.max_len
+        self.emb_auto = nn.Embedding(config.N + 1, config.embed_dim, padding_idx=0)
+        self.emb_cross = nn.Embedding(config.N + 1, config.embed_dim, padding_idx=0)
+        self.emb_inputs = nn.Embedding(4, config.embed_dim, padding_idx=3)
+        self.position_enc_auto = PositionalEncoding(self.embed_dim, n_position=self.block_len)
+        self.position_enc_cross = PositionalEncoding(self.embed_dim, n_position=self.block_len, num=5000)
+        self.dropout = nn.Dropout(p=config.dropout)
+        self.dropout_cross = nn.Dropout(p=config.dropout)
+        d = config.embed_dim // config.n_head
+        self.layer_stack = nn.ModuleList([DecoderLayer(config.embed_dim, config.embed_dim * 4, config.n_head, d, d,
+                                                       dropout=config.dropout) for _ in range(config.n_layers)])
+        self.layer_norm = nn.LayerNorm(config.embed_dim, eps=1e-6)
+        self.layer_norm_cross = nn.LayerNorm(config.embed_dim, eps=1e-6)
+
+    def forward(self, noisy_enc, src_mask, trg_seq, trg_mask, device):
+        """noisy_enc (b, L, E); trg_seq (b, L) of token indices; src_mask, trg_mask (b, L) over the keys."""
+        mem = noisy_enc * self.emb_cross(torch.arange(1, self.block_len + 1, device=device))
+        mem = self.layer_norm_cross(self.dropout_cross(self.position_enc_cross(mem)))
+        x = self.layer_norm(self.dropout(self.position_enc_auto(self.emb_inputs(trg_seq))))
+        for layer in self.layer_stack:
+            x, _, _ = layer(x, mem, slf_attn_mask=_key_mask(trg_mask), dec_enc_attn_mask=_key_mask(src_mask))
+        return x
+
+
+class _FusedXFormer(nn.Module):
+    """What the two classes below share: the coverage of their fused kernels, the refusals and the handle cache."""
+
+    _prefix = ""   # C entry points: <prefix>_create / _destroy
+    _label = ""
+
+    def _init_common(self, config):
+        self.embed_dim = config.embed_dim
+        self.block_len = config.max_len
+        self.N = config.N
+        self.n_head = config.n_head
+        self.n_layers = config.n_layers
+        self._handle = None
+        self._hkey = None
+
+    def fused_reason(self) -> str:
+        """Why the fused kernel does not cover this configuration ('' if it does)."""
+        k = f"the fused {self._label} kernel"
+        if self.embed_dim != 64:
+            return f"embed_dim {self.embed_dim}: {k} is built for embed_dim 64"
+        if self.n_head != 8:
+            return f"n_head {self.n_head}: {k} is built for 8 heads"
+        if self.block_len != self.N:
+            return f"max_len {self.block_len} != N {self.N}: {k} needs max_len == N"
+        if self.N not in (16, 32, 64):
+            return f"N {self.N}: {k} covers N in (16, 32, 64)"
+        if not 1 <= self.n_layers <= 8:
+            return f"n_layers {self.n_layers}: {k} covers 1 .. 8 layers"
+        return ""
+
+    def fused_supported(self) -> bool:
+        return self.fused_reason() == ""
+
+    def _get_handle(self, device):
+        tensors = list(self.parameters()) + list(self.buffers())
+        key = (str(device), tuple(p._version for p in tensors), tuple(p.data_ptr() for p in tensors))
+        if self._handle is None or self._hkey != key:
+            W = self._packed()
+            out = ctypes.c_void_p()
+            L = _lib.load()
+            with torch.cuda.device(device):
+                _lib.check(getattr(L, self._prefix + "_create")(int(self.N), int(self.embed_dim), int(self.n_head),
+                                                                int(self.n_layers), W.ctypes.data_as(ctypes.c_void_p),
+                                                                int(W.size), ctypes.byref(out)),
+                           self._prefix + "_create")
+            if self._handle is not None:
+                getattr(L, self._prefix + "_destroy")(self._handle)
+            self._handle, self._hkey = out, key
+        return self._handle
+
+    def __del__(self):
+        try:
+            if self._handle is not None:
+                getattr(_lib.load(), self._prefix + "_destroy")(self._handle)
+        except Exception:
+            pass
+
+    def _check_mask(self, mask):
+        """Every test-time caller passes an all-ones mask (run_models.py:326); anything else is refused."""
+        if mask is not None and not bool(torch.as_tensor(mask).all()):
+            raise _lib.NpdError(f"the fused {self._label} path takes an all-ones mask (run_models.py:326)")
+
+    def _check(self, y):
+        """The refusals every fused call makes, before anything moves to the device."""
+        reason = self.fused_reason()
+        if reason:
+            raise _lib.NpdError(reason)
+        if self.training:
+            raise _lib.NpdError(f"the fused {self._label} path is inference-only (eval mode)")
+        if y.dim() != 2 or y.shape[1] != self.N:
+            raise ValueError("input must be (B, N) with N = config.N")
+
+    @staticmethod
+    def _layer_parts(a, at, ff=None):
+        parts = [a(at.w_qs.weight), a(at.w_ks.weight), a(at.w_vs.weight), a(at.fc.weight), a(at.layer_norm.weight),
+                 a(at.layer_norm.bias)]
+        if ff is not None:
+            parts += [a(ff.w_1.weight), a(ff.w_1.bias), a(ff.w_2.weight), a(ff.w_2.bias), a(ff.layer_norm.weight),
+                      a(ff.layer_norm.bias)]
+        return parts
+
+
+def _flat(t):
+    return t.detach().float().cpu().numpy().ravel()
+
+
+class XFormerEndToEndEncoder(_FusedXFormer):
+    """Drop-in for models.XFormerEndToEndEncoder (models.py:662-686, ``--model encoder``): one pass over the N tokens,
+    a logit for each.  ``decode`` / ``logits`` run in one launch of libnpd's fused kernel (npd_xfenc_forward);
+    ``forward`` (the training-time API, any mask) is plain torch.  The kernel covers embed_dim 64, n_head 8,
+    N = max_len in {16, 32, 64}, 1 .. 8 layers; anything else raises NpdError -- there is no eager fall-back."""
+
+    _prefix, _label = "npd_xfenc", "encoder"
+
+    def __init__(self, config):
+        super().__init__()
+        self._init_common(config)
+        self.Encoder = XFormerEncoder(config)
+        self.Lin_Decoder = nn.Linear(config.embed_dim, 1)
+
+    def forward(self, noisy_enc, mask, trg_seq, device):
+        """models.py:671-681: (output (B,N,2), decoded_msg_bits (B,N,1), mask, logits (B,N,1))."""
+        x = torch.ones(self.embed_dim, device=device) * noisy_enc.unsqueeze(-1)
+        logits = self.Lin_Decoder(self.Encoder(x, mask, device))
+        out = torch.sigmoid(logits)
+        return torch.cat((1 - out, out), -1), logits.sign(), mask, logits
+
+    def _packed(self) -> np.ndarray:
+        """The weights npd_xfenc_create reads, in the order include/npd.h documents."""
+        a, enc = _flat, self.Encoder
+        parts = [a(enc.pos_emb.weight), a(enc.position_enc.pos_table[0, :self.N]), a(enc.layer_norm.weight),
+                 a(enc.layer_norm.bias)]
+        for layer in enc.layer_stack:
+            parts += self._layer_parts(a, layer.slf_attn, layer.pos_ffn)
+        parts += [a(self.Lin_Decoder.weight), a(self.Lin_Decoder.bias)]
+        return np.ascontiguousarray(np.concatenate(parts), dtype=np.float32)
+
+    def logits(self, y):
+        """(logits (B,N), bits (B,N)): the sign is taken at every position, frozen ones included."""
+        self._check(y)
+        yd = _lib.f32c(_lib.stage(y, "noisy_enc"))
+        B = yd.shape[0]
+        h = self._get_handle(yd.device)
+        bits = torch.empty(B, self.N, dtype=torch.float32, device=yd.device)
+        lg = torch.empty_like(bits)
+        with torch.cuda.device(yd.device):
+            _lib.check(_lib.load().npd_xfenc_forward(h, _lib.ptr(yd), _lib.ptr(bits), _lib.ptr(lg), B,
+                                                     _lib.stream_of(yd.device)), "npd_xfenc_forward")
+        return _lib.home(lg, y), _lib.home(bits, y)
+
+    def decode(self, noisy_enc, info_positions, mask, device, trg_seq=None):
+        """models.py:683-686: (decoded_msg_bits (B,N,1), mask); an all-ones mask only."""
+        self._check_mask(mask)
+        _, bits = self.logits(noisy_enc)
+        return bits.unsqueeze(-1), mask
+
+
+class XFormerEndToEndDecoder(_FusedXFormer):
+    """Drop-in for models.XFormerEndToEndDecoder (models.py:599-654, ``--model decoder``): autoregressive, with
+    cross-attention over an embedding of y in every layer.  ``decode`` / ``decode_logits`` run the whole successive
+    decode in one launch of libnpd's fused kernel (npd_xfdec_decode); ``forward`` (teacher-forced, each word expanded
+    to max_len rows; the training-time API) is plain torch.  Coverage and refusals as for the encoder."""
+
+    _prefix, _label = "npd_xfdec", "decoder"
+
+    def __init__(self, config):
+        super().__init__()
+        self._init_common(config)
+        self.trg_pad_idx = 3
+        self.start_idx = 2
+        self.Decoder = XFormerDecoder(config)
+        self.Lin_Decoder = nn.Linear(config.embed_dim, 1)
+
+    def forward(self, noisy_enc, mask, trg_seq, device):
+        """models.py:609-633.  Word b becomes max_len rows; row b max_len + t holds the tokens built from
+        trg_seq[b, :-1] behind the start token, with the keys <= t, so its logit at position t is the decode's at step
+        t along that path.  Returns (output (B L, L, 2), decoded_msg_bits (B L, L, 1), out_mask (B L, L) -- one at
+        position t of row b L + t --, logits (B L, L, 1))."""
+        B = trg_seq.size(0)
+        idx = torch.cat((torch.full((B, 1), self.start_idx, dtype=torch.long, device=device),
+                         (trg_seq[:, :-1] == 1).long()), -1)
+        L = idx.size(1)
+        causal = torch.tril(torch.ones((1, L, L), device=device)).bool()
+        trg_mask = ((idx != self.trg_pad_idx).unsqueeze(-2) & causal).reshape(B * L, L)
+        shifted = torch.cat((trg_mask[:, 1:].float(), torch.zeros((B * L, 1), device=device)), -1)
+        idx = idx.repeat_interleave(L, 0)
+        y = noisy_enc.repeat_interleave(L, 0)
+        src_mask = torch.as_tensor(mask, device=device).repeat_interleave(L, 0)
+        x = torch.ones(self.embed_dim, device=device) * y.unsqueeze(-1)
+        logits = self.Lin_Decoder(self.Decoder(x, src_mask, idx, trg_mask, device))
+        out = torch.sigmoid(logits)
+        return torch.cat((1 - out, out), -1), logits.sign(), trg_mask.float() - shifted, logits
+
+    def _packed(self) -> np.ndarray:
+        """The weights npd_xfdec_create reads, in the order include/npd.h documents."""
+        a, dec = _flat, self.Decoder
+        parts = [a(dec.emb_cross.weight), a(dec.position_enc_cross.pos_table[0, :self.N]),
+                 a(dec.layer_norm_cross.weight), a(dec.layer_norm_cross.bias), a(dec.emb_inputs.weight),
+                 a(dec.position_enc_auto.pos_table[0, :self.N]), a(dec.layer_norm.weight), a(dec.layer_norm.bias)]
+        for layer in dec.layer_stack:
+            parts += self._layer_parts(a, layer.slf_attn) + self._layer_parts(a, layer.enc_attn, layer.pos_ffn)
+        parts += [a(self.Lin_Decoder.weight), a(self.Lin_Decoder.bias)]
+        return np.ascontiguousarray(np.concatenate(parts), dtype=np.float32)
+
+    _is_info = XFormerEndToEndGPT._is_info
+
+    def decode_logits(self, y, info_positions, forced=None):
+        """(bits (B,N), logits (B,N)) of the successive decode; logits are 0 and bits +1 at frozen positions.  With
+        ``forced`` (B,N) of +-1, token j is built from forced[:, j-1] instead of the decision (the bits returned are
+        still the signs of the logits)."""
+        self._check(y)
+        is_info = self._is_info(info_positions)
+        if forced is not None and tuple(forced.shape) != tuple(y.shape):
+            raise ValueError("forced must be (B, N)")
+        yd = _lib.f32c(_lib.stage(y, "noisy_enc"))
+        B = yd.shape[0]
+        fd = None if forced is None else _lib.f32c(_lib.stage(forced, "forced", yd.device))
+        h = self._get_handle(yd.device)
+        bits = torch.empty(B, self.N, dtype=torch.float32, device=yd.device)
+        lg = torch.empty_like(bits)
+        with torch.cuda.device(yd.device):
+            _lib.check(_lib.load().npd_xfdec_decode(h, _lib.ptr(yd), is_info.ctypes.data_as(ctypes.c_void_p),
+                                                    _lib.ptr(fd), _lib.ptr(bits), _lib.ptr(lg), B,
+                                                    _lib.stream_of(yd.device)), "npd_xfdec_decode")
+        return _lib.home(bits, y), _lib.home(lg, y)
+
+    def decode(self, noisy_enc, info_positions, mask, device):
+        """models.py:635-654: (output_bits (B,N), mask); an all-ones mask only."""
+        self._check_mask(mask)
         bits, _ = self.decode_logits(noisy_enc, info_positions)
         return bits, mask

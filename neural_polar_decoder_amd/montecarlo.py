@@ -336,6 +336,33 @@ class GPTMonteCarlo(DecoderMonteCarlo):
         return self.net.decode_logits(y, self.info_np)[0]
 
 
+class XFormerMonteCarlo(DecoderMonteCarlo):
+    """Encoder / decoder transformer decoding (run_models.py:338-346, testXformer with --model encoder / decoder):
+    ``net.decode``'s bits at the info positions vs the message.  The encoder model returns (B,N,1): the counted bits
+    are bits[:, info, 0]."""
+
+    def __init__(self, code, net, snrs, total_cw, batch, seed=1234, rank=None, world=None, device=None):
+        super().__init__(code, snrs, total_cw, batch, seed, rank, world, device)
+        if not net.fused_supported():
+            from ._lib import NpdError
+            raise NpdError(net.fused_reason())
+        self.net = net
+
+    def decisions(self, y):
+        bits = self.net.decode(y, self.info_np, torch.ones_like(y).long(), y.device)[0]
+        return bits[:, :, 0] if bits.dim() == 3 else bits
+
+
+def seeded_xformer(model, N, n_layers=6, seed=0, device="cuda"):
+    """XFormerEndToEndEncoder / XFormerEndToEndDecoder (models.py:662-686 / :599-654; embed_dim 64, 8 heads, the
+    reference's defaults) with PyTorch-default-initialised weights under torch.manual_seed(seed)."""
+    from .models import XFormerEndToEndDecoder, XFormerEndToEndEncoder
+    cls = {"encoder": XFormerEndToEndEncoder, "decoder": XFormerEndToEndDecoder}[model]
+    torch.manual_seed(seed)
+    cfg = argparse.Namespace(embed_dim=64, max_len=N, N=N, n_head=8, n_layers=n_layers, dropout=0.0, model=model)
+    return cls(cfg).to(device).eval()
+
+
 def seeded_gpt(N, n_layers=6, seed=0, device="cuda"):
     """XFormerEndToEndGPT (models.py:340-423; embed_dim 64, 8 heads, the reference's defaults) with
     PyTorch-default-initialised weights under torch.manual_seed(seed)."""
@@ -368,7 +395,8 @@ def seeded_conv(N, embed_dim=128, seed=0, device="cuda"):
 
 def _parse_args(argv=None):
     ap = argparse.ArgumentParser(description="MI355X BER/BLER Monte-Carlo (SC, SC-List, exact-LSE SC, ML, bitwise MAP, "
-                                             "CRISP GRU, CRISP GRU list, convNet, GPT transformer decoders)")
+                                             "CRISP GRU, CRISP GRU list, convNet, GPT / encoder / decoder "
+                                             "transformer decoders)")
     ap.add_argument("--code", choices=["polar", "pac"], default="polar")
     ap.add_argument("--N", type=int, default=64)
     ap.add_argument("--K", type=int, default=32)
@@ -407,6 +435,13 @@ def _parse_args(argv=None):
     ap.add_argument("--gpt_checkpoint", default=None, help="run_models.py checkpoint ({'xformer', 'args'}, model gpt) "
                                                            "for --gpt")
     ap.add_argument("--gpt_layers", type=int, default=6, help="--gpt without checkpoint: transformer layers (1 .. 8)")
+    ap.add_argument("--xformer", choices=["encoder", "decoder"], default=None,
+                    help="also run the encoder or decoder transformer model (run_models.py:338, --model encoder / "
+                         "decoder; N in 16, 32, 64)")
+    ap.add_argument("--xformer_checkpoint", default=None, help="run_models.py checkpoint ({'xformer', 'args'}, model "
+                                                               "encoder or decoder) for --xformer")
+    ap.add_argument("--xformer_layers", type=int, default=6, help="--xformer without checkpoint: transformer layers "
+                                                                  "(1 .. 8)")
     ap.add_argument("--init_seed", type=int, default=0, help="torch seed of the untrained (seeded) decoder weights")
     a = ap.parse_args(argv)
     if a.crc_len is not None:
@@ -507,6 +542,20 @@ def _main(argv=None):
         if not gnet.fused_supported():
             raise SystemExit("--gpt: " + gnet.fused_reason())
         gpt = GPTMonteCarlo(code, gnet, snrs, a.test_size, a.batch_size, a.seed).run()
+    xf = None
+    if a.xformer:
+        if a.xformer_checkpoint:
+            from .datasets import xformer_from_checkpoint
+            xnet = xformer_from_checkpoint(a.xformer_checkpoint)
+            if type(xnet).__name__ != "XFormerEndToEnd" + a.xformer.capitalize():
+                raise SystemExit("--xformer_checkpoint holds another model than --xformer " + a.xformer)
+            if xnet.N != a.N:
+                raise SystemExit("--xformer_checkpoint was trained for a different N")
+        else:
+            xnet = seeded_xformer(a.xformer, a.N, a.xformer_layers, a.init_seed)
+        if not xnet.fused_supported():
+            raise SystemExit("--xformer: " + xnet.fused_reason())
+        xf = XFormerMonteCarlo(code, xnet, snrs, a.test_size, a.batch_size, a.seed).run()
     if _dist() is None or _dist().get_rank() == 0:
         print("Test SNRs : ", snrs)
         if crisp is not None:
@@ -550,6 +599,10 @@ def _main(argv=None):
             print("BERs of GPT Xformer: {0}".format(gpt.ber))
             print("BLERs of GPT Xformer: {0}".format(gpt.bler))
             rec["gpt"] = dict(gpt.as_dict(), n_layers=gnet.n_layers)
+        if xf is not None:
+            print("BERs of {0} Xformer: {1}".format(a.xformer, xf.ber))
+            print("BLERs of {0} Xformer: {1}".format(a.xformer, xf.bler))
+            rec["xformer_" + a.xformer] = dict(xf.as_dict(), n_layers=xnet.n_layers)
         print(json.dumps(rec))
     return res
 
