@@ -417,6 +417,40 @@ int npd_gru_list_supported(const npd_gru* gru, const npd_code* code, int list_si
 int npd_gru_list_decode(const npd_gru* gru, const npd_code* code, const float* y, const float* fy, int list_size,
                         float* msg_hat, int32_t* sel, float* cand_msg, float* cand_metric, int64_t B, void* stream);
 /*
+ * CRC-aided CRISP GRU list decoding.  The reference has no such decoder (its CRC helpers do not run and its
+ * list_decode takes no CRC), so, as for CRC-aided SC-List decode above, this header defines it.
+ * Polynomial, bit convention and CRC layout are exactly those of "CRC-aided SC-List decode": crc_poly bit i is the
+ *   coefficient of x^i, 1 <= c <= 24, bit 0 set, c < K (anything else NPD_EINVAL); symbol -1 is bit 1; the K information
+ *   slots in sorted-information-set order carry K-c message bits and then the c CRC bits; for PAC codes the CRC covers
+ *   the message before the convolution, i.e. the path's v bits.
+ * The list is npd_gru_list_decode's, bit for bit: forking, metrics, pruneLists, tie rules and list order.
+ * A path passes if its K information bits, read as a polynomial of degree K-1, leave remainder 0 (list paths hold +-1
+ *   only, so there is no 0 decision).  Unused slots (2^K < list_size) do not pass.
+ * Selection.  The first minimum, in list order, of ||encode(msg) - y||^2 -- the same fp32 distance the plain epilogue
+ *   computes -- over the passing live paths; if no live path passes, the first minimum over all live paths, which is
+ *   exactly npd_gru_list_decode's choice; crc_ok = 1 or 0 accordingly.  The rule is distance, not metric: the GRU
+ *   list's metrics are sums of |out| penalties, not likelihoods, and the plain decoder already chooses by distance;
+ *   the CRC only restricts the candidate set.  A caller who wants another rule takes the candidates.
+ * npd_gru_list_decode_crc outputs, each optional but at least one of msg_hat and cand_msg: msg_hat (B,K) (the CRC
+ *   columns included, as npd_scl_decode_crc), sel (B) and crc_ok (B) int32, cand_msg (B, list_size, K) and cand_metric
+ *   (B, list_size) as npd_gru_list_decode, cand_crc (B, list_size) int32: each candidate's remainder register (0: it
+ *   passes), -1 for unused slots.  crc_poly = 0 is NPD_EINVAL.
+ * npd_gru_list_decode_crc_mc decodes, chooses and counts in one launch: counters[0..2] (device uint64, not reset) +=
+ *   {bit errors over the K-c message bits against the Philox message of (seed, cw_offset + word), as
+ *   npd_scl_decode_crc_mc regenerates it; block errors over the same bits; words with crc_ok == 0}.  msg_hat (B,K) is
+ *   optional.  Here only, crc_poly = 0 is allowed: plain selection (npd_gru_list_decode's), counts over all K bits,
+ *   counters[2] untouched.
+ * Limits and error behaviour are npd_gru_list_decode's: the same handles (NPD_ENOTSUP for those the list kernels
+ * refuse), 1 <= list_size <= 8, y / fy 16-byte aligned, NULL and polynomial checks before any HIP call, stream-ordered,
+ * no allocation, B = 0 returns NPD_OK.
+ */
+int npd_gru_list_decode_crc(const npd_gru* gru, const npd_code* code, const float* y, const float* fy, int list_size,
+                            uint32_t crc_poly, float* msg_hat, int32_t* sel, int32_t* crc_ok, float* cand_msg,
+                            float* cand_metric, int32_t* cand_crc, int64_t B, void* stream);
+int npd_gru_list_decode_crc_mc(const npd_gru* gru, const npd_code* code, const float* y, const float* fy, int list_size,
+                               uint32_t crc_poly, float* msg_hat, uint64_t seed, uint64_t cw_offset, int64_t B,
+                               unsigned long long* counters, void* stream);
+/*
  * One layer of RNN_Model.get_h0 / get_Fy (rnn_all.py:362-385): out (B, Nout) = act(x (B, K) W^T + bias), W (Nout, K)
  * row-major, all device fp32, k summed in order.  act: 0 linear, 1 relu, 2 selu, 3 elu, 4 tanh, 5 sigmoid
  * (RNN_Model.act, rnn_all.py:346-360).  get_h0 follows layer ii with act iff ii != y_depth (rnn_all.py:364-368): every

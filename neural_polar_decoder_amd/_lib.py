@@ -74,6 +74,10 @@ SIGNATURES = [
     ("npd_gru_list_supported", c_int, [c_void_p, c_void_p, c_int]),
     ("npd_gru_list_decode", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_i64, c_void_p]),
+    ("npd_gru_list_decode_crc", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_u32, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
+    ("npd_gru_list_decode_crc_mc", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_u32, c_void_p, c_u64, c_u64,
+                                           c_i64, c_void_p, c_void_p]),
     ("npd_ymlp_layer", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_void_p]),
     ("npd_conv_create", c_int, [c_int, c_int, c_void_p, c_i64, c_int, ctypes.POINTER(c_void_p)]),
     ("npd_conv_destroy", c_int, [c_void_p]),

@@ -18,7 +18,8 @@
 // lane half; the gather is skipped when no lane of the wave moves.
 //
 // This file also owns the C entry points of both list kernels; hidden 256 / 512 handles go to gru_wide_list_kernel
-// (npd_gru_wide_list.hip: the same column map and procedure on the weight-streaming step).
+// (npd_gru_wide_list.hip: the same column map and procedure on the weight-streaming step).  npd_gru_list_decode_crc
+// and npd_gru_list_decode_crc_mc run the CA instantiations: the same step loop, list_finish<true> as the epilogue.
 #include <stdlib.h>
 #include <string.h>
 
@@ -27,7 +28,8 @@
 namespace npd {
 namespace gru {
 
-template <int F, int L>
+// CA: list_finish's CRC-aided / counting epilogue (npd_gru_list.hpp); the step loop is the same text in both
+template <int F, int L, bool CA>
 __global__ __launch_bounds__(64 * NPD_GRU_WPB) void gru_list_kernel(const ListArgs a) {
     constexpr int WPB = NPD_GRU_WPB;
     using G = Geo<F, L>;
@@ -57,6 +59,8 @@ __global__ __launch_bounds__(64 * NPD_GRU_WPB) void gru_list_kernel(const ListAr
         return f16v{x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3],
                     x2[0], x2[1], x2[2], x2[3], x3[0], x3[1], x3[2], x3[3]};
     };
+
+    [[maybe_unused]] unsigned long long cnt[3] = {0ull, 0ull, 0ull};  // CA: this wave's error counts (wave-uniform)
 
     for (int64_t tile = (int64_t)blockIdx.x * WPB + wave; tile < ntiles; tile += (int64_t)gridDim.x * WPB) {
         const int64_t cw = tile * cpt + (col >> lpl);
@@ -181,15 +185,19 @@ __global__ __launch_bounds__(64 * NPD_GRU_WPB) void gru_list_kernel(const ListAr
         }
 
         // ================= epilogue: encode every path, distance to y, first minimum over the live slots
-        list_finish(a, bw, met, ls, cw, cwc, valid, half, slot, base);
+        if constexpr (CA)
+            list_finish<true>(a, bw, met, ls, cw, cwc, valid, half, slot, base, cnt);
+        else
+            list_finish(a, bw, met, ls, cw, cwc, valid, half, slot, base);
     }
+    if constexpr (CA) list_count_flush(a, cnt, lane);
 }
 
-template <int F, int L>
+template <int F, int L, bool CA>
 static int launch_list(const ListArgs& a, hipStream_t s) {
     using G = Geo<F, L>;
     constexpr int WPB = NPD_GRU_WPB;
-    auto kern = gru_list_kernel<F, L>;
+    auto kern = gru_list_kernel<F, L, CA>;
     const size_t lds = (size_t)G::TOTAL * 4;
     static bool attr = false;
     if (!attr) {
@@ -221,32 +229,34 @@ extern "C" int npd_gru_list_supported(const npd_gru* gru, const npd_code* code, 
     return (list_handle_ok(gru) && code->p.N == gru->N && list_size >= 1 && list_size <= 8) ? 1 : 0;
 }
 
-extern "C" int npd_gru_list_decode(const npd_gru* g, const npd_code* code, const float* y, const float* fy,
-                                   int list_size, float* msg_hat, int32_t* sel, float* cand_msg, float* cand_metric,
-                                   int64_t B, void* stream) {
-    NPD_ARG(g != nullptr, "npd_gru_list_decode: gru is NULL");
-    NPD_ARG(code != nullptr, "npd_gru_list_decode: code is NULL");
-    NPD_ARG(B >= 0, "npd_gru_list_decode: B < 0");
-    NPD_ARG(list_size >= 1 && list_size <= 8, "npd_gru_list_decode: list_size must be 1 .. 8");
-    NPD_ARG(code->p.N == g->N, "npd_gru_list_decode: the code's N differs from the GRU handle's");
+// The checks, the argument block and the launch that the three entry points share.  `a` arrives with the caller's output
+// pointers, polynomial and counting fields; need_out: at least one of msg_hat and cand_msg must be given (the counting
+// entry point needs neither).  ca: the CRC-aided / counting instantiations.
+static int list_run(const char* who, const npd_gru* g, const npd_code* code, const float* y, const float* fy,
+                    int list_size, gru::ListArgs a, bool need_out, bool ca, int64_t B, void* stream) {
+    const std::string w(who);
+    NPD_ARG(g != nullptr, w + ": gru is NULL");
+    NPD_ARG(code != nullptr, w + ": code is NULL");
+    NPD_ARG(B >= 0, w + ": B < 0");
+    NPD_ARG(list_size >= 1 && list_size <= 8, w + ": list_size must be 1 .. 8");
+    NPD_ARG(code->p.N == g->N, w + ": the code's N differs from the GRU handle's");
+    if (a.crc_poly != 0u) {
+        a.crc_c = crc_degree(a.crc_poly, code->p.K);
+        NPD_ARG(a.crc_c > 0, w + ": crc_poly needs degree 1 .. 24 below K and bit 0 set");
+    }
     if (!list_handle_ok(g))
-        return fail(NPD_ENOTSUP, "npd_gru_list_decode: list decoding runs on the fp32 GRU kernels (GRU cell, precision 0, "
-                                 "F 32, 64, 256 or 512, plain Linear head)");
+        return fail(NPD_ENOTSUP, w + ": list decoding runs on the fp32 GRU kernels (GRU cell, precision 0, "
+                                     "F 32, 64, 256 or 512, plain Linear head)");
     if (B == 0) return NPD_OK;
-    NPD_ARG(msg_hat != nullptr || cand_msg != nullptr, "npd_gru_list_decode: msg_hat and cand_msg both NULL");
-    NPD_ARG(y != nullptr, "npd_gru_list_decode: y is NULL");
+    NPD_ARG(!need_out || a.msg_hat != nullptr || a.cand_msg != nullptr, w + ": msg_hat and cand_msg both NULL");
+    NPD_ARG(y != nullptr, w + ": y is NULL");
     if (fy == nullptr) fy = y;
-    NPD_ARG(((uintptr_t)y & 15) == 0 && ((uintptr_t)fy & 15) == 0, "npd_gru_list_decode: y and fy must be 16-byte aligned");
-    NPD_ARG(B <= (int64_t)1 << 40, "npd_gru_list_decode: B too large");
-    gru::ListArgs a{};
+    NPD_ARG(((uintptr_t)y & 15) == 0 && ((uintptr_t)fy & 15) == 0, w + ": y and fy must be 16-byte aligned");
+    NPD_ARG(B <= (int64_t)1 << 40, w + ": B too large");
     a.img = g->img;
     a.wy = reinterpret_cast<const gru::f4*>(g->wy);
     a.y = y;
     a.fy = fy;
-    a.msg_hat = msg_hat;
-    a.sel = sel;
-    a.cand_msg = cand_msg;
-    a.cand_metric = cand_metric;
     a.B = B;
     a.N = g->N;
     a.K = code->p.K;
@@ -257,11 +267,54 @@ extern "C" int npd_gru_list_decode(const npd_gru* g, const npd_code* code, const
     a.b_lin = g->b_lin;
     a.tapmask = code->p.tapmask;
     a.smask = code->p.smask;
-    for (int w = 0; w < kMaxWords; ++w) a.info[w] = 0;
+    for (int w2 = 0; w2 < kMaxWords; ++w2) a.info[w2] = 0;
     for (int i = 0; i < g->N; ++i)
         if (!((code->p.frozen[i >> 5] >> (i & 31)) & 1u)) a.info[i >> 5] |= 1u << (i & 31);
     hipStream_t s = (hipStream_t)stream;
-    if (g->F > 64) return gru::launch_wide_list(g, a, s);
-    return gru::dispatch(gru::NarrowShapes{}, [&](auto f, auto l) { return gru::launch_list<f.value, l.value>(a, s); },
-                         g->F, g->layers);
+    if (g->F > 64) return gru::launch_wide_list(g, a, ca, s);
+    if (ca)
+        return gru::dispatch(gru::NarrowShapes{},
+                             [&](auto f, auto l) { return gru::launch_list<f.value, l.value, true>(a, s); }, g->F,
+                             g->layers);
+    return gru::dispatch(gru::NarrowShapes{},
+                         [&](auto f, auto l) { return gru::launch_list<f.value, l.value, false>(a, s); }, g->F, g->layers);
+}
+
+extern "C" int npd_gru_list_decode(const npd_gru* g, const npd_code* code, const float* y, const float* fy,
+                                   int list_size, float* msg_hat, int32_t* sel, float* cand_msg, float* cand_metric,
+                                   int64_t B, void* stream) {
+    gru::ListArgs a{};
+    a.msg_hat = msg_hat;
+    a.sel = sel;
+    a.cand_msg = cand_msg;
+    a.cand_metric = cand_metric;
+    return list_run("npd_gru_list_decode", g, code, y, fy, list_size, a, true, false, B, stream);
+}
+
+extern "C" int npd_gru_list_decode_crc(const npd_gru* g, const npd_code* code, const float* y, const float* fy,
+                                       int list_size, uint32_t crc_poly, float* msg_hat, int32_t* sel, int32_t* crc_ok,
+                                       float* cand_msg, float* cand_metric, int32_t* cand_crc, int64_t B, void* stream) {
+    NPD_ARG(crc_poly != 0u, "npd_gru_list_decode_crc: crc_poly needs degree 1 .. 24 below K and bit 0 set");
+    gru::ListArgs a{};
+    a.msg_hat = msg_hat;
+    a.sel = sel;
+    a.crc_ok = crc_ok;
+    a.cand_msg = cand_msg;
+    a.cand_metric = cand_metric;
+    a.cand_crc = cand_crc;
+    a.crc_poly = crc_poly;
+    return list_run("npd_gru_list_decode_crc", g, code, y, fy, list_size, a, true, true, B, stream);
+}
+
+extern "C" int npd_gru_list_decode_crc_mc(const npd_gru* g, const npd_code* code, const float* y, const float* fy,
+                                          int list_size, uint32_t crc_poly, float* msg_hat, uint64_t seed,
+                                          uint64_t cw_offset, int64_t B, unsigned long long* counters, void* stream) {
+    NPD_ARG(counters != nullptr, "npd_gru_list_decode_crc_mc: counters is NULL");
+    gru::ListArgs a{};
+    a.msg_hat = msg_hat;
+    a.counters = counters;
+    a.seed = seed;
+    a.cw_offset = cw_offset;
+    a.crc_poly = crc_poly;  // 0: plain selection, counted over all K bits
+    return list_run("npd_gru_list_decode_crc_mc", g, code, y, fy, list_size, a, false, true, B, stream);
 }

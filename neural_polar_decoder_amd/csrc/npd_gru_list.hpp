@@ -1,6 +1,8 @@
 // npd_gru_list.hpp -- what the two GRU list kernels share (npd_gru_list.hip: gru_list_kernel, weights in LDS, F <= 64;
 // npd_gru_wide_list.hip: gru_wide_list_kernel, weights streamed, F = 256 / 512): the launch arguments, the pruning
-// order and the tie rule.  npd_gru_list.hip owns the C entry points and dispatches to launch_wide_list.
+// order, the tie rule and the epilogue in its two modes (plain, and CRC-aided selection with fused error counting:
+// include/npd.h, "CRC-aided CRISP GRU list decoding").  npd_gru_list.hip owns the C entry points and dispatches to
+// launch_wide_list.
 #pragma once
 
 #include "npd_gru_host.hpp"
@@ -24,6 +26,13 @@ struct ListArgs {
     float b_lin;
     uint32_t tapmask, smask;
     uint32_t info[kMaxWords];
+    // CRC-aided selection and fused counting (the CA instantiations only; npd_gru_list_decode_crc / _crc_mc)
+    int32_t* crc_ok;    // (B) or NULL
+    int32_t* cand_crc;  // (B, L) or NULL
+    unsigned long long* counters;  // 3 device counters, or NULL: no counting
+    uint64_t seed, cw_offset;      // Philox message stream of the words counted against
+    uint32_t crc_poly;             // bit i = coefficient of x^i; 0 with crc_c = 0: plain selection
+    int crc_c;                     // its degree
 };
 
 typedef float f8v __attribute__((ext_vector_type(8)));
@@ -103,10 +112,39 @@ __device__ __forceinline__ int list_prune(float& met, uint32_t& neg, bool& flip,
     return src;
 }
 
+// remainder of a path's information bits (bw at the set bits of a.info, wave-uniform), read as a polynomial of degree
+// K - 1: npd_scl.hpp's crc_divide recurrence on a register of crc_c bits plus the bit shifted out
+__device__ __forceinline__ uint32_t list_crc_divide(const ListArgs& a, const uint32_t (&bw)[kMaxWords]) {
+    uint32_t reg = 0u;
+#pragma unroll
+    for (int w = 0; w < kMaxWords; ++w)
+        if (32 * w < a.N)
+            for (uint32_t im = a.info[w]; im != 0u; im &= im - 1u) {
+                reg = (reg << 1) | ((bw[w] >> __builtin_ctz(im)) & 1u);
+                reg ^= a.crc_poly & (0u - ((reg >> a.crc_c) & 1u));
+            }
+    return reg;
+}
+
+// word q of the Philox message words (a select chain: no dynamically indexed register array)
+__device__ __forceinline__ uint32_t list_pick_word(const uint32_t (&mw)[8], int q) {
+    uint32_t w = mw[0];
+#pragma unroll
+    for (int i = 1; i < 8; ++i) w = (q == i) ? mw[i] : w;
+    return w;
+}
+
 // The end of list_decode for one wave's columns: encode every path (bw: its bit words), fp32 distance to y, first
 // minimum over the codeword's ls live slots, and the optional outputs (lane half 0 of the valid columns stores).
+// CA (npd_gru_list_decode_crc / _crc_mc; the CA = false instantiations compile to what they were): with a.crc_c > 0
+// every column divides its own path's information bits, and when a ballot of the pass flags finds a passing path in
+// the codeword's slot group the first minimum runs over the passing slots only; with a.counters the chosen column
+// compares its first K - crc_c information bits with the Philox message words and the wave's sums go to cnt[0..2]
+// (wave-uniform; the kernel adds them to a.counters once, after its last tile).
+template <bool CA = false>
 __device__ __forceinline__ void list_finish(const ListArgs& a, const uint32_t (&bw)[kMaxWords], float met, int ls,
-                                            int64_t cw, int64_t cwc, bool valid, int half, int slot, int base) {
+                                            int64_t cw, int64_t cwc, bool valid, int half, int slot, int base,
+                                            unsigned long long* cnt = nullptr) {
     const int N = a.N;
     uint32_t cd[kMaxWords];
 #pragma unroll
@@ -166,12 +204,36 @@ __device__ __forceinline__ void list_finish(const ListArgs& a, const uint32_t (&
     const float dist = ds + __shfl_xor(ds, 32, 64);
     float best = 0.0f;
     int bsel = 0;
+    [[maybe_unused]] uint32_t reg = 0u;
+    [[maybe_unused]] bool anyp = false;
+    if constexpr (!CA) {
 #pragma unroll
-    for (int t = 0; t < 8; ++t) {
-        const float dt = __shfl(dist, base + (t < ls ? t : 0), 64);
-        if (t == 0 || (t < ls && dt < best)) {
-            best = t == 0 ? dt : (dt < best ? dt : best);
-            bsel = t;
+        for (int t = 0; t < 8; ++t) {
+            const float dt = __shfl(dist, base + (t < ls ? t : 0), 64);
+            if (t == 0 || (t < ls && dt < best)) {
+                best = t == 0 ? dt : (dt < best ? dt : best);
+                bsel = t;
+            }
+        }
+    } else {
+        // eligible slots of this codeword: the passing ones if any passes, else every live one (slot 0 is always live,
+        // so with no passing path this is the plain scan, comparison for comparison)
+        uint32_t emask = (1u << ls) - 1u;
+        if (a.crc_c > 0) {
+            reg = list_crc_divide(a, bw);
+            const uint32_t pm = (uint32_t)(__ballot(slot < ls && reg == 0u) >> base) & emask;
+            anyp = pm != 0u;
+            emask = anyp ? pm : emask;
+        }
+        bool found = false;
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+            const float dt = __shfl(dist, base + (t < ls ? t : 0), 64);
+            if (((emask >> t) & 1u) && (!found || dt < best)) {
+                best = dt;
+                bsel = t;
+                found = true;
+            }
         }
     }
     if (half == 0 && valid && slot < a.L) {
@@ -179,6 +241,10 @@ __device__ __forceinline__ void list_finish(const ListArgs& a, const uint32_t (&
         const bool chosen = slot == bsel;
         if (a.cand_metric) a.cand_metric[cw * a.L + slot] = alive ? met : __builtin_inff();
         if (a.sel && chosen) a.sel[cw] = bsel;
+        if constexpr (CA) {
+            if (a.cand_crc) a.cand_crc[cw * a.L + slot] = alive ? (int32_t)reg : -1;
+            if (a.crc_ok && chosen) a.crc_ok[cw] = anyp ? 1 : 0;
+        }
         float* cm = a.cand_msg ? a.cand_msg + (cw * a.L + slot) * (int64_t)a.K : nullptr;
         float* mh = (a.msg_hat && chosen) ? a.msg_hat + cw * (int64_t)a.K : nullptr;
         int k = 0;
@@ -195,10 +261,51 @@ __device__ __forceinline__ void list_finish(const ListArgs& a, const uint32_t (&
                     }
             }
     }
+    if constexpr (CA) {
+        if (a.counters) {
+            // message words of this column's codeword: Philox block 0 holds bits 0 .. 127, block 1 bits 128 .. 255
+            const int kc = a.K - a.crc_c;
+            uint32_t mw[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int blk = 0; blk < 2; ++blk)
+                if (blk * 128 < kc) {
+                    const u32x4 o = philox_block(a.seed, kStreamMsg, a.cw_offset + (uint64_t)cwc, (uint32_t)blk);
+                    mw[4 * blk + 0] = o.x;
+                    mw[4 * blk + 1] = o.y;
+                    mw[4 * blk + 2] = o.z;
+                    mw[4 * blk + 3] = o.w;
+                }
+            uint32_t e = 0u, cur = mw[0];
+            int k = 0;
+#pragma unroll
+            for (int w = 0; w < kMaxWords; ++w)
+                if (32 * w < N)
+                    for (uint32_t im = a.info[w]; im != 0u; im &= im - 1u) {
+                        e += (k < kc) ? (((bw[w] >> __builtin_ctz(im)) ^ cur) & 1u) : 0u;
+                        cur >>= 1;
+                        ++k;
+                        if ((k & 31) == 0) cur = list_pick_word(mw, k >> 5);
+                    }
+            const bool mine = half == 0 && valid && slot == bsel;
+            e = mine ? e : 0u;
+            cnt[0] += (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_sum_u32(e));
+            cnt[1] += (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_sum_u32(e ? 1u : 0u));
+            cnt[2] += (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_sum_u32((mine && !anyp) ? 1u : 0u));
+        }
+    }
+}
+
+// the wave's sums of list_finish<true>, added once: one atomic triple per wave (counters[2] only with a CRC)
+__device__ __forceinline__ void list_count_flush(const ListArgs& a, const unsigned long long* cnt, int lane) {
+    if (a.counters && lane == 0) {
+        atomicAdd(a.counters + 0, cnt[0]);
+        atomicAdd(a.counters + 1, cnt[1]);
+        if (a.crc_c > 0) atomicAdd(a.counters + 2, cnt[2]);
+    }
 }
 
 // npd_gru_wide_list.hip: F = 256 / 512, 1 or 2 layers
-int launch_wide_list(const npd_gru* g, const ListArgs& a, hipStream_t s);
+int launch_wide_list(const npd_gru* g, const ListArgs& a, bool ca, hipStream_t s);
 
 }  // namespace gru
 }  // namespace npd

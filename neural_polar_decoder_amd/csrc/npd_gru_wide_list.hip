@@ -21,7 +21,8 @@
 namespace npd {
 namespace gru {
 
-template <int F, int L>
+// CA: list_finish's CRC-aided / counting epilogue (npd_gru_list.hpp), run by wave 0 like the plain one
+template <int F, int L, bool CA>
 __global__ __launch_bounds__(64 * WideGeo<F>::NW) void gru_wide_list_kernel(const ListArgs a) {
     using G = Geo<F, L>;
     using WG = WideGeo<F>;
@@ -51,6 +52,7 @@ __global__ __launch_bounds__(64 * WideGeo<F>::NW) void gru_wide_list_kernel(cons
     const f16v zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     const float one_or_zero = half ? 0.0f : 1.0f;
     constexpr int R = 0, Z = 1, IN = 2, HN = 3;
+    [[maybe_unused]] unsigned long long cnt[3] = {0ull, 0ull, 0ull};  // CA: wave 0's error counts (wave-uniform)
 
     for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int64_t cw = tile * cpt + (col >> lpl);
@@ -177,15 +179,23 @@ __global__ __launch_bounds__(64 * WideGeo<F>::NW) void gru_wide_list_kernel(cons
         }
 
         // ================= epilogue (every wave holds every column's path: wave 0 finishes them)
-        if (wave == 0) list_finish(a, bw, met, ls, cw, cwc, valid, half, slot, base);
+        if (wave == 0) {
+            if constexpr (CA)
+                list_finish<true>(a, bw, met, ls, cw, cwc, valid, half, slot, base, cnt);
+            else
+                list_finish(a, bw, met, ls, cw, cwc, valid, half, slot, base);
+        }
+    }
+    if constexpr (CA) {
+        if (wave == 0) list_count_flush(a, cnt, lane);
     }
 }
 
 // one tile of 32 >> lp_log2 codewords per workgroup of NW waves, as many workgroups per CU as LDS and registers allow
-template <int F, int L>
+template <int F, int L, bool CA>
 static int launch_wide_list_tiles(const npd_gru* g, const ListArgs& a, hipStream_t s) {
     constexpr int NW = WideGeo<F>::NW;
-    constexpr auto kern = gru_wide_list_kernel<F, L>;
+    constexpr auto kern = gru_wide_list_kernel<F, L, CA>;
     const size_t lds = (size_t)wide_lds_bytes(g->N, F, L);
     int occ = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, 64 * NW, lds) != hipSuccess || occ <= 0) {
@@ -197,10 +207,13 @@ static int launch_wide_list_tiles(const npd_gru* g, const ListArgs& a, hipStream
                             lds, s, a);
 }
 
-int launch_wide_list(const npd_gru* g, const ListArgs& a, hipStream_t s) {
+int launch_wide_list(const npd_gru* g, const ListArgs& a, bool ca, hipStream_t s) {
     using Shapes = Combos<Combo<512, 2>, Combo<512, 1>, Combo<256, 2>, Combo<256, 1>>;  // WideShapes without F = 128
-    return dispatch(Shapes{}, [&](auto f, auto l) { return launch_wide_list_tiles<f.value, l.value>(g, a, s); }, g->F,
-                    g->layers);
+    if (ca)
+        return dispatch(Shapes{}, [&](auto f, auto l) { return launch_wide_list_tiles<f.value, l.value, true>(g, a, s); },
+                        g->F, g->layers);
+    return dispatch(Shapes{}, [&](auto f, auto l) { return launch_wide_list_tiles<f.value, l.value, false>(g, a, s); },
+                    g->F, g->layers);
 }
 
 }  // namespace gru

@@ -309,6 +309,35 @@ class GRUListMonteCarlo(GRUMonteCarlo):
         return MonteCarlo.count_sweep(self, cw_offset, n, counters)
 
 
+class CAGRUListMonteCarlo(GRUListMonteCarlo):
+    """CRC-aided CRISP GRU list decoding of a code whose CRC is set (code.set_crc): generate with the CRC
+    (npd_mc_generate_crc, y only) + RNN_decoder.list_decode_crc_mc (decode, choose by CRC and distance, and count in
+    one launch; --use_ynn nets feed the y-MLP's output to the GRU).  The errors are counted over the K - CRC_len
+    message bits (MCResult.K); the third counter is the words no list path passed for (``crc_fail``, one per SNR
+    point, set by run())."""
+
+    def __init__(self, code, net, decoder, list_size, snrs, total_cw, batch, seed=1234, rank=None, world=None,
+                 device=None):
+        if not getattr(code, "CRC_len", 0):
+            raise ValueError("CAGRUListMonteCarlo needs a code with a CRC: call code.set_crc(CRC_len) first")
+        super().__init__(code, net, decoder, list_size, snrs, total_cw, batch, seed, rank, world, device)
+        self.K = code.K_minus_CRC
+        self.crc_len = code.CRC_len
+        self.crc_fail = None
+
+    def new_counters(self):
+        return torch.zeros(len(self.snrs), 3, dtype=torch.int64, device=self.device)
+
+    def count_batch(self, si, snr, cw_offset, n, counters_row):
+        _, _, y = self.code.mc_generate_crc(n, snr, self.seed, si, cw_offset, device=self.device, want_msg=False)
+        self.decoder.list_decode_crc_mc(self.net, y, self.code, self.list_size, self.seed, cw_offset, counters_row)
+
+    def run(self) -> MCResult:
+        res = super().run()
+        self.crc_fail = [int(v) for v in self.last_counters[:, 2]]
+        return res
+
+
 class ConvMonteCarlo(DecoderMonteCarlo):
     """convNet decoding (run_models.py:333-337, testXformer): sign of the LayerNorm output at the info
     positions vs the message."""
@@ -412,7 +441,8 @@ def _parse_args(argv=None):
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--list_size", type=int, default=None, help="also run SC-List with this list size, 1 .. 32 (Polar and PAC)")
     ap.add_argument("--crc_len", type=int, default=None, choices=[3, 6, 8, 11, 16, 24],
-                    help="with --list_size: also run CRC-aided SC-List with a CRC of this many bits "
+                    help="with --list_size: also run CRC-aided SC-List with a CRC of this many bits; with --crisp "
+                         "--rnn_list_size: also run the CRC-aided GRU list decoder "
                          "(CRC_polynomials; the message shrinks to K - crc_len bits)")
     ap.add_argument("--lse", action="store_true", help="also run the exact-LSE sc_decode (Polar, polar.py:209)")
     ap.add_argument("--hard_decision", action="store_true", help="exact-LSE SC with sign decisions (else tanh)")
@@ -445,8 +475,8 @@ def _parse_args(argv=None):
     ap.add_argument("--init_seed", type=int, default=0, help="torch seed of the untrained (seeded) decoder weights")
     a = ap.parse_args(argv)
     if a.crc_len is not None:
-        if not a.list_size:
-            ap.error("--crc_len needs --list_size (it chooses among the list's paths)")
+        if not a.list_size and not (a.crisp and a.rnn_list_size):
+            ap.error("--crc_len needs --list_size or --crisp --rnn_list_size (it chooses among a list's paths)")
         if a.crc_len >= a.K:
             ap.error("--crc_len must be below K")
     if a.rnn_list_size is not None:
@@ -501,7 +531,7 @@ def _main(argv=None):
         if not code.ml_supported(map=True):
             raise SystemExit("--bitwise_map: bitwise MAP covers N in {8, 16, 32, 64} with K <= 16")
         bmap = MAPMonteCarlo(code, snrs, a.test_size, a.batch_size, a.seed).run()
-    crisp = crispl = None
+    crisp = crispl = carnnl = carnnl_fail = None
     if a.crisp:
         if a.crisp_checkpoint:
             from .datasets import rnn_from_checkpoint
@@ -522,6 +552,11 @@ def _main(argv=None):
         crisp = GRUMonteCarlo(code, net, dec, snrs, a.test_size, a.batch_size, a.seed).run()
         if a.rnn_list_size:
             crispl = GRUListMonteCarlo(code, net, dec, a.rnn_list_size, snrs, a.test_size, a.batch_size, a.seed).run()
+            if a.crc_len:
+                code.set_crc(a.crc_len)
+                drv = CAGRUListMonteCarlo(code, net, dec, a.rnn_list_size, snrs, a.test_size, a.batch_size, a.seed)
+                carnnl, carnnl_fail = drv.run(), drv.crc_fail
+                code.set_crc(0)
     conv = None
     if a.conv:
         if a.conv_checkpoint:
@@ -592,6 +627,10 @@ def _main(argv=None):
             print("BERs of RNN List decoding: {0}".format(crispl.ber))
             print("BLERs of RNN List decoding: {0}".format(crispl.bler))
             rec["crisp_gru_list"] = dict(crispl.as_dict(), list_size=a.rnn_list_size)
+        if carnnl is not None:
+            print("BERs of CRC-aided RNN List decoding: {0}".format(carnnl.ber))
+            print("BLERs of CRC-aided RNN List decoding: {0}".format(carnnl.bler))
+            rec["ca_rnnl"] = dict(carnnl.as_dict(), list_size=a.rnn_list_size, crc_len=a.crc_len, crc_fail=carnnl_fail)
         if conv is not None:
             print("BLERs of Xformer: {0}".format(conv.bler))
             rec["conv"] = conv.as_dict()

@@ -376,32 +376,40 @@ class RNN_decoder:
         """True when list_decode(net, y, code, L) runs on the fused kernel (no handle is built)."""
         return self._list_reason(net, L) is None
 
-    def list_decode(self, net, y, code, L=1, return_candidates=False):
-        """rnn_all.RNN_decoder.list_decode (rnn_all.py:580-664) in one fused launch (npd_gru_list_decode): the (B, K)
-        +-1 messages of the list survivor nearest to y.  `code` is this package's PolarCode or PAC (its information set
-        and encoder drive the final selection).  return_candidates: also (cand_msg (B, L, K), cand_metric (B, L),
-        sel (B) int32) -- the final list in the reference's order; unused slots (2^K < L) hold metric +inf, message 0.
-        Unidirectional fp32 GRU nets with the plain Linear head at feature_size 32 / 64 (weights in LDS) and 256 / 512
-        (weights streamed, the greedy decoder's N limit); list_supported(net, L) tells beforehand."""
+    def _list_setup(self, net, y, code, L, who="list_decode"):
+        """The checks and staging every list entry point shares: (y, fy, code handle, GRU handle).  Refusals first
+        (_list_reason), before any GPU work."""
         why = self._list_reason(net, L)
         if why is not None:
             raise _lib.NpdError(why)
-        L = int(L)
         if net.input_size != self.N + 1 + int(self.onehot):
             raise ValueError("net.input_size must be N + 1 + onehot")
         ch = code._code_for(code.B) if hasattr(code, "pac_encode") else code.code
         info = np.sort(np.asarray(self.info_inds, np.int64).reshape(-1))
         if ch.N != self.N or not np.array_equal(info, ch.info):
-            raise _lib.NpdError("list_decode: the decoder's info_inds are not the code's information positions")
-        y_in = y
+            raise _lib.NpdError(f"{who}: the decoder's info_inds are not the code's information positions")
         y = _lib.f32c(_lib.stage(y, "y"))
         if y.dim() != 2 or y.shape[1] != self.N:
             raise ValueError(f"y must be (batch, {self.N}), got {tuple(y.shape)}")
         if y.data_ptr() % 16:
             y = y.clone()
         fy = _ymlp_forward(net, y) if net.y_depth > 0 else None  # --use_ynn: Fy feeds the GRU, y the final selection
+        return y, fy, ch, self._handle(net, y.device)
+
+    def list_decode(self, net, y, code, L=1, return_candidates=False, use_CRC=False):
+        """rnn_all.RNN_decoder.list_decode (rnn_all.py:580-664) in one fused launch (npd_gru_list_decode): the (B, K)
+        +-1 messages of the list survivor nearest to y.  `code` is this package's PolarCode or PAC (its information set
+        and encoder drive the final selection).  return_candidates: also (cand_msg (B, L, K), cand_metric (B, L),
+        sel (B) int32) -- the final list in the reference's order; unused slots (2^K < L) hold metric +inf, message 0.
+        Unidirectional fp32 GRU nets with the plain Linear head at feature_size 32 / 64 (weights in LDS) and 256 / 512
+        (weights streamed, the greedy decoder's N limit); list_supported(net, L) tells beforehand.  ``use_CRC=True``
+        after code.set_crc / encode_with_crc is list_decode_crc (as scl_decode's keyword)."""
+        if use_CRC:
+            return self.list_decode_crc(net, y, code, L, return_candidates=return_candidates)
+        y_in = y
+        y, fy, ch, h = self._list_setup(net, y, code, L)
+        L = int(L)
         B, K = y.shape[0], ch.K
-        h = self._handle(net, y.device)
         hat = torch.empty(B, K, dtype=torch.float32, device=y.device)
         cm = cmet = sel = None
         if return_candidates:
@@ -415,6 +423,66 @@ class RNN_decoder:
         if return_candidates:
             return hat, (_lib.home(cm, y_in), _lib.home(cmet, y_in), _lib.home(sel, y_in))
         return hat
+
+    @staticmethod
+    def _crc_of(code):
+        """(polynomial, CRC length) of a code with a CRC set; _CRCSurface's ValueError otherwise."""
+        need = getattr(code, "_need_crc", None)
+        if need is None:
+            raise ValueError("no CRC is set: the code has no CRC surface (PolarCode or PAC with set_crc)")
+        need()
+        return int(code.crc_poly), int(code.CRC_len)
+
+    def list_decode_crc(self, net, y, code, L=1, return_ok=False, return_candidates=False):
+        """CRC-aided GRU list decoding (npd_gru_list_decode_crc, include/npd.h): list_decode's list, bit for bit, and
+        of its passing paths the one nearest to y (the first in list order), or list_decode's own choice when no path
+        passes.  `code` must have a CRC set (set_crc / encode_with_crc); returns the (B, K - CRC_len) message, then
+        crc_ok (B) int32 with ``return_ok=True``, then (cand_msg (B, L, K), cand_metric (B, L), sel (B) int32,
+        cand_crc (B, L) int32: each candidate's remainder, 0 = passes, -1 = unused slot) with
+        ``return_candidates=True``."""
+        poly, c = self._crc_of(code)
+        y_in = y
+        y, fy, ch, h = self._list_setup(net, y, code, L, "list_decode_crc")
+        L = int(L)
+        B, K = y.shape[0], ch.K
+        dev = y.device
+        hat = torch.empty(B, K, dtype=torch.float32, device=dev)
+        ok = torch.empty(B, dtype=torch.int32, device=dev) if return_ok else None
+        cm = cmet = sel = ccrc = None
+        if return_candidates:
+            cm = torch.empty(B, L, K, dtype=torch.float32, device=dev)
+            cmet = torch.empty(B, L, dtype=torch.float32, device=dev)
+            sel = torch.empty(B, dtype=torch.int32, device=dev)
+            ccrc = torch.empty(B, L, dtype=torch.int32, device=dev)
+        _lib.check(_lib.load().npd_gru_list_decode_crc(h.h, ch.h, _lib.ptr(y), _lib.ptr(fy), L, poly, _lib.ptr(hat),
+                                                       _lib.ptr(sel), _lib.ptr(ok), _lib.ptr(cm), _lib.ptr(cmet),
+                                                       _lib.ptr(ccrc), B, _lib.stream_of(dev)),
+                   "npd_gru_list_decode_crc")
+        out = (_lib.home(hat[:, :K - c], y_in),)
+        if return_ok:
+            out += (_lib.home(ok, y_in),)
+        if return_candidates:
+            out += ((_lib.home(cm, y_in), _lib.home(cmet, y_in), _lib.home(sel, y_in), _lib.home(ccrc, y_in)),)
+        return out[0] if len(out) == 1 else out
+
+    def list_decode_crc_mc(self, net, y, code, L, seed, cw_offset, counters, msg_hat=None):
+        """counters[0..2] += {bit errors, block errors over the K - CRC_len message bits against the Philox messages of
+        codewords cw_offset .. cw_offset + batch - 1, words no path passed for}: list_decode_crc and the count in one
+        launch (npd_gru_list_decode_crc_mc).  A code without a CRC (CRC_len 0) counts list_decode's choice over all K
+        bits and leaves counters[2] alone.  msg_hat (B, K) is optional."""
+        poly = int(getattr(code, "crc_poly", 0)) if getattr(code, "CRC_len", 0) else 0
+        why = self._list_reason(net, L)
+        if why is not None:
+            raise _lib.NpdError(why)
+        _lib.require_gpu(y, "y")
+        y, fy, ch, h = self._list_setup(net, y, code, L, "list_decode_crc_mc")
+        _lib.check_out(counters, "counters", torch.int64, 3, y.device)
+        _lib.check_out(msg_hat, "msg_hat", torch.float32, y.shape[0] * ch.K, y.device, optional=True)
+        _lib.check(_lib.load().npd_gru_list_decode_crc_mc(h.h, ch.h, _lib.ptr(y), _lib.ptr(fy), int(L), poly,
+                                                          _lib.ptr(msg_hat), int(seed), int(cw_offset), y.shape[0],
+                                                          _lib.ptr(counters), _lib.stream_of(y.device)),
+                   "npd_gru_list_decode_crc_mc")
+        return counters
 
     def _h0(self, net, y):
         """(B, F * layers) initial states: get_h0's MLP (y first when the net was built with skip, rnn_all.py:369-370),
