@@ -460,6 +460,48 @@ int npd_gru_list_decode_crc_mc(const npd_gru* gru, const npd_code* code, const f
 int npd_ymlp_layer(const float* x, const float* W, const float* bias, float* out, int64_t B, int K, int Nout, int act,
                    void* stream);
 
+/* ---------------------------------------------------------------------------------- CRISP GRU training */
+typedef struct npd_gru_train npd_gru_train; /* the plan of one shape: the device buffers of the kernels' weight images */
+/*
+ * RNN_decoder.decode(net, True, y, gt, teacher_forcing_ratio) (rnn_all.py:422-512), differentiable: decoding_type
+ * y_input without the y-MLP, GRU cells, unidirectional, the plain Linear(F, 1) head, no LayerNorm, no dropout, fp32.
+ * N a multiple of 8 in [8, 256], F 32 or 64, 1 or 2 layers (anything else NPD_EINVAL).  The plan holds no weights: every
+ * call takes them as one flat DEVICE vector in npd_gru_create's order (per layer weight_ih | weight_hh | bias_ih |
+ * bias_hh, then linear.weight | linear.bias) and packs its images from it on the device, so a call after an optimiser
+ * step sees the new weights with no host copy and no synchronisation.  One plan serves one stream at a time.
+ * npd_gru_train_destroy(NULL) is an argument error (NPD_EINVAL), not a no-op.
+ */
+int npd_gru_train_create(int N, int F, int layers, int onehot, npd_gru_train** out);
+int npd_gru_train_destroy(npd_gru_train* plan);
+/*
+ * Sizes (in floats) of the two caller-owned device buffers of a batch of B words: `saved` (forward writes, backward
+ * reads: per step and layer h', r, z, n and W_hn h + b_hn, and the fed inputs: N B (5 layers F + 3) floats) and `scratch`
+ * (backward's own: the gate gradients, N B (4 F layers + 1) floats, and the contraction's partial sums).  Both must be
+ * 16-byte aligned; their layout is the library's.
+ */
+int npd_gru_train_workspace(const npd_gru_train* plan, int64_t B, int64_t* saved_floats, int64_t* scratch_floats);
+/*
+ * Forward, everything in the step frame ii = 0 .. N-1 (under reverse_order the caller flips gt before and out after).
+ * Step 0 is fed +1; step ii + 1 is fed bits[:, ii] = gt[:, ii] (student = 0, values in {-1, 0, +1}) or
+ * sign(out[:, ii]) (student = 1); with onehot, -1 and 0 feed column 0 and +1 column 1 (get_onehot).  out[:, ii] is step
+ * ii's logit where writes_logit[ii] (HOST, N bytes) is set and the constant 1.0 elsewhere (student forcing writes
+ * the information steps only, rnn_all.py:493; teacher forcing every step).  y, gt, out, bits: device (B, N) fp32, y
+ * 16-byte aligned; gt may be NULL when student = 1.  Two launches (image packing, the fused N-step forward); B = 0
+ * returns NPD_OK with no launch.
+ */
+int npd_gru_train_forward(npd_gru_train* plan, const float* weights_dev, const float* y, const float* gt_or_null,
+                          const uint8_t* writes_logit, int student, float* out, float* bits, float* saved, int64_t B,
+                          void* stream);
+/*
+ * Backward of the forward that filled `saved` (same weights_dev, y, B): grad_out (B, N) device, step frame, and 0 where
+ * the forward wrote no logit.  grad_weights_dev (flat, the weights' order and length) is OVERWRITTEN with the gradient
+ * of sum(grad_out * out).  Four launches: image packing, the fused backward recurrence, the weight-gradient
+ * contraction into per-workgroup partial sums and their reduction in a fixed order (no floating-point atomics: equal
+ * calls return equal bits).  B = 0 zeroes the gradient.
+ */
+int npd_gru_train_backward(npd_gru_train* plan, const float* weights_dev, const float* y, const float* grad_out,
+                           const float* saved, float* scratch, float* grad_weights_dev, int64_t B, void* stream);
+
 /* ---------------------------------------------------------------------------------- conv model */
 /*
  * convNet (models.py:691-772) forward/decode.  weights: host fp32 in state_dict order

@@ -79,6 +79,13 @@ SIGNATURES = [
     ("npd_gru_list_decode_crc_mc", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_u32, c_void_p, c_u64, c_u64,
                                            c_i64, c_void_p, c_void_p]),
     ("npd_ymlp_layer", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_int, c_int, c_void_p]),
+    ("npd_gru_train_create", c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(c_void_p)]),
+    ("npd_gru_train_destroy", c_int, [c_void_p]),
+    ("npd_gru_train_workspace", c_int, [c_void_p, c_i64, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
+    ("npd_gru_train_forward", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                      c_void_p, c_i64, c_void_p]),
+    ("npd_gru_train_backward", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64,
+                                       c_void_p]),
     ("npd_conv_create", c_int, [c_int, c_int, c_void_p, c_i64, c_int, ctypes.POINTER(c_void_p)]),
     ("npd_conv_destroy", c_int, [c_void_p]),
     ("npd_conv_workspace_bytes", c_i64, [c_void_p, c_i64]),

@@ -229,7 +229,8 @@ class _GruHandle:
 
 class RNN_decoder:
     """rnn_all.RNN_decoder (rnn_all.py:400-561): eval (``train=False``) decoding for decoding_type
-    'y_input' runs fused on the GPU.
+    'y_input' runs fused on the GPU; training (``train=True``, rnn_all.py:422-512) is differentiable on the fused
+    training kernels (npd_gru_train_forward / _backward) for the configurations train_supported(net) accepts.
 
     ``precision`` (keyword, not in the reference): "fp32" (default; the reference's arithmetic),
     "fp16x3" (hi + lo fp16 split on the fp16 MFMA: three products per multiply, fp32 accumulation; F = 64 with 2
@@ -272,10 +273,91 @@ class RNN_decoder:
             self._cache[key] = h
         return h
 
-    def decode(self, net, train, y, gt=None, teacher_forcing_ratio=0., loss_inds=None, return_logits=False):
+    # ------------------------------------------------------------------ training (rnn_all.py:422-512)
+    def train_reason(self, net):
+        """Why decode(net, True, ...) refuses this configuration (None: it runs on the fused training kernels,
+        npd_gru_train_forward / _backward) -- checked before any GPU call."""
+        if self.decoding_type != "y_input":
+            return (f"fused training covers decoding_type 'y_input', got {self.decoding_type!r} (the y-MLP of 'y_h0' / "
+                    "'y_h0_out' has no backward kernel yet: a follow-up)")
+        if self.precision != "fp32":
+            return f"fused training runs fp32; the split precisions are a follow-up, got precision {self.precision!r}"
+        if getattr(net, "rnn_type", None) != "GRU":
+            return "fused training covers GRU cells; LSTM cells are a follow-up"
+        if getattr(net, "bidirectional", False):
+            return "fused training covers unidirectional nets, not --bidirectional"
+        if getattr(net, "y_depth", 0) > 0:
+            return "fused training does not cover the y-MLP (--use_ynn, y_depth > 0): a follow-up"
+        if isinstance(getattr(net, "layernorm", None), nn.LayerNorm):
+            return "fused training does not cover the LayerNorm head (--use_layernorm)"
+        if getattr(net, "out_linear_depth", 1) != 1:
+            return "fused training covers the plain Linear(F, 1) head, not out_linear_depth > 1"
+        if getattr(net, "output_size", 1) != 1:
+            return "fused training needs output_size 1"
+        if net.feature_size not in (32, 64):
+            return ("fused training keeps the weights in LDS: feature_size 32 or 64 (128 to 512 are a follow-up), got "
+                    f"{net.feature_size}")
+        if net.num_rnn_layers not in (1, 2):
+            return f"fused training covers 1 or 2 GRU layers, got {net.num_rnn_layers}"
+        if float(net.drop.p) != 0.0:
+            return f"fused training has no dropout mask: net.drop.p must be 0, got {net.drop.p}"
+        if not (8 <= self.N <= 256 and self.N % 8 == 0):
+            return f"fused training needs N a multiple of 8 in [8, 256], got {self.N}"
+        if net.input_size != self.N + 1 + int(self.onehot):
+            return f"net.input_size must be N + 1 + onehot = {self.N + 1 + int(self.onehot)}, got {net.input_size}"
+        return None
+
+    def train_supported(self, net) -> bool:
+        """True when decode(net, True, ...) runs on the fused training kernels (no GPU call)."""
+        return self.train_reason(net) is None
+
+    def _decode_train(self, net, y, gt, teacher_forcing_ratio, return_path=False):
+        """decode(net, True, y, gt, tfr): one fused forward launch now, one fused backward recurrence and the
+        weight-gradient contraction when the result's .backward() runs.  (B, N) fp32 with a grad_fn; with return_path
+        also bits (B, N), step frame: the value step ii handed to step ii + 1."""
+        import random
+        why = self.train_reason(net)
+        if why is not None:
+            raise _lib.NpdError(why)
+        net.train()
+        teacher = random.random() < teacher_forcing_ratio  # the reference's one draw per call (rnn_all.py:425)
+        if getattr(y, "requires_grad", False):
+            raise _lib.NpdError("fused training returns no gradient for y: y.requires_grad must be False")
+        dev = next(net.parameters()).device
+        if dev.type != "cuda":
+            raise _lib.NpdError("fused training needs the net on the GPU: libnpd has no CPU path")
+        y = _lib.f32c(_lib.stage(y.detach(), "y", dev))
+        if y.dim() != 2 or y.shape[1] != self.N:
+            raise ValueError(f"y must be (batch, {self.N}), got {tuple(y.shape)}")
+        if y.data_ptr() % 16:
+            y = y.clone()
+        g = None
+        if teacher:
+            if gt is None:
+                raise ValueError("teacher forcing needs gt")
+            g = _lib.f32c(_lib.stage(gt.detach(), "gt", dev))
+            if g.shape != y.shape:
+                raise ValueError(f"gt must be {tuple(y.shape)}, got {tuple(g.shape)}")
+            if self.reverse_order:
+                g = g.flip(1).contiguous()
+        writes = np.ones(self.N, np.uint8)
+        if not teacher:  # student forcing writes step ii iff ii (not jj) is an information index (rnn_all.py:493)
+            writes[:] = 0
+            writes[np.asarray(self.info_inds, np.int64).reshape(-1)] = 1
+        if y.shape[0] == 0:
+            out = bits = torch.empty(0, self.N, dtype=torch.float32, device=dev)
+        else:
+            params = _train_params(net)
+            plan = _train_plan(dev, self.N, net.feature_size, net.num_rnn_layers, self.onehot)
+            out, bits = _GruTrainFn.apply(plan, y, g, writes, *params)
+        if self.reverse_order:
+            out = out.flip(1)
+        return (out, bits) if return_path else out
+
+    def decode(self, net, train, y, gt=None, teacher_forcing_ratio=0., loss_inds=None, return_logits=False,
+               return_path=False):
         if train:
-            raise _lib.NpdError("RNN_decoder.decode(train=True) is the training path (out of scope for the fused "
-                                "decoder); use the reference's PyTorch loop for training")
+            return self._decode_train(net, y, gt, teacher_forcing_ratio, return_path)
         if self.decoding_type not in ("y_input", "y_h0"):
             raise _lib.NpdError(f"fused decode supports decoding_type 'y_input' and 'y_h0', got {self.decoding_type!r}"
                                 " ('y_h0_out' builds a (1 + depth) F y-MLP that get_h0 cannot reshape, rnn_all.py:1324)")
@@ -513,6 +595,97 @@ def _ymlp_forward(net: RNN_Model, y: torch.Tensor) -> torch.Tensor:
                                         W.shape[1], W.shape[0], act, _lib.stream_of(y.device)), "npd_ymlp_layer")
         x = out
     return x
+
+
+class _TrainPlan:
+    """npd_gru_train handle of one (N, F, layers, onehot): the kernels' device image buffers, no weights."""
+
+    def __init__(self, N, F, layers, onehot):
+        out = ctypes.c_void_p()
+        _lib.check(_lib.load().npd_gru_train_create(int(N), int(F), int(layers), 1 if onehot else 0, ctypes.byref(out)),
+                   "npd_gru_train_create")
+        self.h = out
+
+    def workspace(self, B):
+        sv, sc = ctypes.c_int64(), ctypes.c_int64()
+        _lib.check(_lib.load().npd_gru_train_workspace(self.h, int(B), ctypes.byref(sv), ctypes.byref(sc)),
+                   "npd_gru_train_workspace")
+        return sv.value, sc.value
+
+    def __del__(self):
+        try:
+            if self.h:
+                _lib.load().npd_gru_train_destroy(self.h)
+        except Exception:
+            pass
+
+
+_TRAIN_PLANS = {}
+
+
+def _train_plan(device, N, F, layers, onehot):
+    """One plan per (device, N, F, layers, onehot); the weights are passed per call, so nothing is keyed on them."""
+    key = (str(device), int(N), int(F), int(layers), bool(onehot))
+    plan = _TRAIN_PLANS.get(key)
+    if plan is None:
+        with torch.cuda.device(device):
+            plan = _TRAIN_PLANS[key] = _TrainPlan(N, F, layers, onehot)
+    return plan
+
+
+def _train_params(net):
+    """The parameters in the flat vector's order (include/npd.h npd_gru_create)."""
+    ps = []
+    for l in range(net.num_rnn_layers):
+        ps += [getattr(net.rnn, f"{nm}_l{l}") for nm in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
+    return ps + [net.linear.weight, net.linear.bias]
+
+
+class _GruTrainFn(torch.autograd.Function):
+    """(out, bits) = npd_gru_train_forward(flat weights, y, gt); backward = npd_gru_train_backward: per-parameter views
+    of the flat gradient.  Everything is in the step frame; the caller flips."""
+
+    @staticmethod
+    def forward(ctx, plan, y, gt, writes, *params):
+        dev = y.device
+        B, N = y.shape
+        flat = torch.cat([p.detach().reshape(-1) for p in params]).to(torch.float32).contiguous()
+        n_saved, n_scratch = plan.workspace(B)
+        saved = torch.empty(n_saved, dtype=torch.float32, device=dev)
+        out = torch.empty(B, N, dtype=torch.float32, device=dev)
+        bits = torch.empty(B, N, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().npd_gru_train_forward(plan.h, _lib.ptr(flat), _lib.ptr(y), _lib.ptr(gt),
+                                                         writes.ctypes.data_as(ctypes.c_void_p), 0 if gt is not None else 1,
+                                                         _lib.ptr(out), _lib.ptr(bits), _lib.ptr(saved), B,
+                                                         _lib.stream_of(dev)), "npd_gru_train_forward")
+        ctx.plan, ctx.y, ctx.flat, ctx.saved_ws, ctx.n_scratch = plan, y, flat, saved, n_scratch
+        ctx.shapes = [p.shape for p in params]
+        # student forcing: the steps that wrote no logit hold the constant 1.0 and take no gradient
+        ctx.mask = None if bool(writes.all()) else torch.from_numpy(writes.astype(np.float32)).to(dev)
+        ctx.mark_non_differentiable(bits)
+        return out, bits
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout, _gbits):
+        plan, y, dev = ctx.plan, ctx.y, ctx.y.device
+        g = gout.to(torch.float32)
+        if ctx.mask is not None:
+            g = g * ctx.mask
+        g = g.contiguous()
+        scratch = torch.empty(ctx.n_scratch, dtype=torch.float32, device=dev)
+        gflat = torch.empty_like(ctx.flat)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().npd_gru_train_backward(plan.h, _lib.ptr(ctx.flat), _lib.ptr(y), _lib.ptr(g),
+                                                          _lib.ptr(ctx.saved_ws), _lib.ptr(scratch), _lib.ptr(gflat),
+                                                          y.shape[0], _lib.stream_of(dev)), "npd_gru_train_backward")
+        grads, off = [], 0
+        for shp in ctx.shapes:
+            n = int(np.prod(shp))
+            grads.append(gflat[off:off + n].view(shp))
+            off += n
+        return (None, None, None, None) + tuple(grads)
 
 
 def get_onehot(actions):
