@@ -30,6 +30,8 @@ EXTRA_npd_scl_crc_wide := -fno-honor-nans
 EXTRA_npd_scl_crc_pac_wide := -fno-honor-nans
 # the ML/MAP epilogues read every MFMA result on the VALU: keep the accumulators in VGPRs (no v_accvgpr_read per value)
 EXTRA_npd_ml := -mllvm -amdgpu-mfma-vgpr-form=1
+# the two-tile count sweep uses more than 256 registers; its gate updates read every accumulator on the VALU as well
+EXTRA_npd_gru_split16 := -mllvm -amdgpu-mfma-vgpr-form=1
 
 $(OBJDIR)/%.o: $(PKG)/csrc/%.hip $(CHDR)
 	@mkdir -p $(OBJDIR)
@@ -49,7 +51,7 @@ $(ORACLE): oracle/npd_oracle.c oracle/npd_oracle_scl.cpp oracle/npd_oracle_lse.c
 
 asm: $(CSRC)
 	@mkdir -p build/asm
-	for f in $(CSRC); do b=$$(basename $$f .hip); $(HIPCC) $(HIPFLAGS) $$( case $$b in npd_sc*) echo -fno-honor-nans;; esac ) --cuda-device-only -S -o build/asm/$$b.s $$f; done
+	for f in $(CSRC); do b=$$(basename $$f .hip); $(HIPCC) $(HIPFLAGS) $$( case $$b in npd_sc*) echo -fno-honor-nans;; npd_ml|npd_gru_split16) echo -mllvm -amdgpu-mfma-vgpr-form=1;; esac ) --cuda-device-only -S -o build/asm/$$b.s $$f; done
 
 clean:
 	rm -rf build $(LIB) $(ORACLE)

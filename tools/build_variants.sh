@@ -7,7 +7,7 @@ src=$1; shift
 make -j8 lib >/dev/null
 mkdir -p tools/bin
 extra=""
-case $src in npd_sc*|npd_scl) extra=-fno-honor-nans;; esac
+case $src in npd_sc*|npd_scl) extra=-fno-honor-nans;; npd_ml|npd_gru_split16) extra="-mllvm -amdgpu-mfma-vgpr-form=1";; esac
 for v in "$@"; do
   n=${v%%:*}; f=${v#*:}
   mkdir -p build/var_$n

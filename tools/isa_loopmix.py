@@ -15,15 +15,18 @@ for n, l in enumerate(body):
     m = re.match(r"^(\.LBB\S+):", l.strip())
     if m:
         labels[m.group(1)] = n
-best = None
+loops = []
 for n, l in enumerate(body):
     m = re.match(r"^\s*s_cbranch_\w+\s+(\.LBB\S+)|^\s*s_branch\s+(\.LBB\S+)", l)
     if m:
         t = m.group(1) or m.group(2)
         if t in labels and labels[t] < n:
-            span = (labels[t], n)
-            if best is None or span[1] - span[0] > best[1] - best[0]:
-                best = span
+            loops.append((labels[t], n))
+best = max(loops, key=lambda sp: sp[1] - sp[0])
+if "--inner" in sys.argv:  # the largest loop that touches no global memory (gru16p_kernel's count sweep: the step loop)
+    sys.argv.remove("--inner")
+    best = max((sp for sp in loops if not any(re.match(r"\s*(global|flat|buffer)_", x) for x in body[sp[0]:sp[1] + 1])),
+               key=lambda sp: sp[1] - sp[0])
 c = Counter()
 for x in body[best[0]:best[1] + 1]:
     x = x.strip()
