@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "npd_gru_common.hpp"
+#include "npd_launch.hpp"
 
 namespace npd {
 namespace gru {
@@ -34,17 +35,7 @@ using WideShapes = Combos<Combo<512, 2>, Combo<512, 1>, Combo<256, 2>, Combo<256
 using AllShapes = Combos<Combo<512, 2>, Combo<512, 1>, Combo<256, 2>, Combo<256, 1>, Combo<128, 2>, Combo<128, 1>,
                          Combo<64, 2>, Combo<64, 1>, Combo<32, 2>, Combo<32, 1>>;
 
-// one launch of a kernel with a dynamic LDS image; its LDS limit is raised on first use, once per instantiation
-template <auto Kern, typename A>
-int launch_lds(const char* what, int grid, int block, size_t lds, hipStream_t s, const A& a) {
-    static bool attr = false;
-    if (!attr) {
-        NPD_HIP(hipFuncSetAttribute((const void*)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, 163840));
-        attr = true;
-    }
-    hipLaunchKernelGGL(Kern, dim3(grid), dim3(block), lds, s, a);
-    return launch_check(what);
-}
+using npd::launch_lds;  // npd_launch.hpp: shared with the conv family
 
 // ---------------------------------------------------------------------------------- image builders' shared pieces
 // the reference's weight vector (npd_gru_create order): per layer W_ih (gates F x din), W_hh (gates F x F), b_ih, b_hh,

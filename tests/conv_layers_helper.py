@@ -1,5 +1,5 @@
 """Shared by tests/test_conv_layers.py (CPU) and tests/test_conv_layers_gpu.py: the per-layer check of the convNet
-kernels (npd_conv.hip) against float64.
+kernels (npd_conv*.hip) against float64.
 
 The logits sit behind three Linear layers and a LayerNorm, so a defect in one conv layer that is hundreds of times that
 layer's own fp32 rounding still moves them by less than the 1e-5 logit bar (tests/test_conv_layers.py keeps that on

@@ -163,7 +163,7 @@ def test_conv_fp16x3_shapes_vs_oracle(oracle, E, N):
 @pytest.mark.parametrize("E,N", [(64, 128), (128, 256), (80, 64)])
 def test_conv_fp16x3_large_activations(oracle, E, N):
     """Activations far beyond fp16's range (received words x 3e4: conv and Linear inputs up to ~1e5): the split kernels
-    scale each layer's input by 2^SA with SA from the producing kernel's max |a| (npd_conv.hip split_sa), so hi never
+    scale each layer's input by 2^SA with SA from the producing kernel's max |a| (npd_conv_common.hpp split_sa), so hi never
     overflows -- before that fix the fixed 2^4 scale turned every |a| > 4094 into inf and the logits into NaN.  The
     logits stay finite and match the float64 oracle (LayerNorm brings them back to O(1); 1e-4 absolute, the fp32 rounding of
     pre-LayerNorm values ~1e5 x 2^-24 relative to their spread) and the fp32 path's decisions."""

@@ -1,4 +1,4 @@
-"""GPU: every conv decoder layer and kernel variant of npd_conv.hip against float64, per layer (the bar and the shape
+"""GPU: every conv decoder layer and kernel variant of npd_conv*.hip against float64, per layer (the bar and the shape
 table are tests/conv_layers_helper.py's), and the batch sizes, scales and calling conventions the other conv tests
 leave out."""
 import ctypes
