@@ -643,7 +643,11 @@ def _train_params(net):
 
 class _GruTrainFn(torch.autograd.Function):
     """(out, bits) = npd_gru_train_forward(flat weights, y, gt); backward = npd_gru_train_backward: per-parameter views
-    of the flat gradient.  Everything is in the step frame; the caller flips."""
+    of the flat gradient.  Everything is in the step frame; the caller flips.
+
+    The backward reads y again (dW_ih0's y columns).  y is kept with ctx.save_for_backward, not copied: when it is
+    the caller's own contiguous fp32 device tensor and the caller writes into it between decode and .backward(),
+    torch's version counter raises instead of returning a gradient of the wrong y."""
 
     @staticmethod
     def forward(ctx, plan, y, gt, writes, *params):
@@ -659,7 +663,8 @@ class _GruTrainFn(torch.autograd.Function):
                                                          writes.ctypes.data_as(ctypes.c_void_p), 0 if gt is not None else 1,
                                                          _lib.ptr(out), _lib.ptr(bits), _lib.ptr(saved), B,
                                                          _lib.stream_of(dev)), "npd_gru_train_forward")
-        ctx.plan, ctx.y, ctx.flat, ctx.saved_ws, ctx.n_scratch = plan, y, flat, saved, n_scratch
+        ctx.save_for_backward(y)
+        ctx.plan, ctx.flat, ctx.saved_ws, ctx.n_scratch = plan, flat, saved, n_scratch
         ctx.shapes = [p.shape for p in params]
         # student forcing: the steps that wrote no logit hold the constant 1.0 and take no gradient
         ctx.mask = None if bool(writes.all()) else torch.from_numpy(writes.astype(np.float32)).to(dev)
@@ -669,7 +674,8 @@ class _GruTrainFn(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gout, _gbits):
-        plan, y, dev = ctx.plan, ctx.y, ctx.y.device
+        (y,) = ctx.saved_tensors
+        plan, dev = ctx.plan, y.device
         g = gout.to(torch.float32)
         if ctx.mask is not None:
             g = g * ctx.mask

@@ -1,6 +1,7 @@
 """float64 restatement of CRISP GRU training -- RNN_decoder.decode(net, True, y, gt, tfr) (rnn_all.py:422-512) and its
 gradient -- written out explicitly (no autograd), for tests/test_gru_train.py (CPU, against fixtures recorded from the
-reference) and tests/test_gru_train_gpu.py (the fused kernels).
+reference), tests/test_gru_train_gpu.py (the fused kernels) and the SHAPE_CASES of tests/test_gru_train_shapes.py
+(CPU) / tests/test_gru_train_shapes_gpu.py (long codes, large batches, saturated gates; the per-block metric).
 
 Frames.  Everything here is in the step frame ii = 0 .. N-1; under reverse_order the caller flips gt on entry and the
 result on return, as the reference does.  `bits` (B, N) is the fed path: bits[:, ii] is what step ii hands to step
@@ -11,6 +12,7 @@ teacher forcing: every step); elsewhere decoded is the constant 1.0.
 MUTATIONS are wrong variants of the restatement; each must miss a case's gradient bar by a wide margin, so the bar
 tells a dropped term from rounding.
 """
+import collections
 import os
 
 import numpy as np
@@ -28,6 +30,9 @@ MUTATIONS = (
     ("last_word_twice", lambda student, rev: True),      # the last word's weight gradient counted again
     ("student_writes_frozen", lambda student, rev: student),   # student forcing writes (and feeds) every step's logit
     ("ii_jj_swapped", lambda student, rev: student and rev),   # the write test on jj = N-1-ii instead of ii
+    # step N - 1's weight and bias gradient sums without the last two words (the carry unchanged): a short or empty
+    # last partial of the contraction
+    ("tail_samples_dropped", lambda student, rev: True),
 )
 
 
@@ -115,6 +120,10 @@ def backward64(cx, gout, mutation=None):
     wl = W["linear.weight"].reshape(-1)
     for ii in range(N - 1, -1, -1):
         go = gout[:, ii]
+        if mutation == "tail_samples_dropped":
+            wrow = np.ones(B)
+            if ii == N - 1:
+                wrow[-2:] = 0.0
         g["linear.weight"] += ((go * wrow) @ cache[ii][-1]["h"]).reshape(g["linear.weight"].shape)
         g["linear.bias"] += (go * wrow).sum()
         dh[-1] = dh[-1] + go[:, None] * wl[None, :]
@@ -165,14 +174,69 @@ def grad_err(got, ref):
     return worst
 
 
+GATES = ("r", "z", "n")
+
+
+def blocks(grads, F, N):
+    """A gradient dict split into the blocks that different parts of the kernels fill: every weight_ih / weight_hh /
+    bias_ih / bias_hh by rows into the gates r = [0, F), z = [F, 2F), n = [2F, 3F) (`name.r`, ...); the three row blocks
+    of weight_ih_l0 again by columns into the y part [:N] and the fed-bit part [N:] (`name.r.y`, `name.r.bit`, ...);
+    linear.* whole."""
+    out = {}
+    for k, v in grads.items():
+        v = np.asarray(v)
+        if not k.startswith("rnn."):
+            out[k] = v
+            continue
+        assert v.shape[0] == 3 * F, (k, v.shape)
+        for gi, gate in enumerate(GATES):
+            blk = v[gi * F:(gi + 1) * F]
+            if k.endswith("weight_ih_l0"):
+                assert N < blk.shape[1] <= N + 2, (k, v.shape)
+                out[f"{k}.{gate}.y"] = blk[:, :N]
+                out[f"{k}.{gate}.bit"] = blk[:, N:]
+            else:
+                out[f"{k}.{gate}"] = blk
+    return out
+
+
+def _shape_of(grads):
+    """(F, N) of a gradient dict: weight_hh_l0 is (3F, F); weight_ih_l0 is (3F, N + 1 or N + 2) with N a multiple of 8."""
+    F = np.asarray(grads["rnn.weight_hh_l0"]).shape[1]
+    return F, np.asarray(grads["rnn.weight_ih_l0"]).shape[1] // 8 * 8
+
+
+def block_errs(got, ref):
+    """Relative 2-norm error of every block (blocks()) of got against ref, by block name."""
+    F, N = _shape_of(ref)
+    gb, rb = blocks(got, F, N), blocks(ref, F, N)
+    assert sorted(gb) == sorted(rb)
+    errs = {}
+    for k, v in rb.items():
+        assert np.linalg.norm(v.ravel()) > 0.0, f"gradient block {k} is zero"
+        errs[k] = rel_err(gb[k], v)
+    return errs
+
+
+def grad_err_blocks(got, ref):
+    """The largest per-block relative error (blocks()); every reference block must be non-zero.  An error confined
+    to one gate, or to the fed-bit columns, is not diluted by the rest of its tensor."""
+    return max(block_errs(got, ref).values())
+
+
 # ---------------------------------------------------------------------------------- torch fp32 autograd (E_ref)
-def build_net(F, layers, N, onehot, seed=None, sd=None, device="cpu"):
-    """The package's RNN_Model: PyTorch-default draws under `seed`, or the given state dict."""
+def build_net(F, layers, N, onehot, seed=None, sd=None, device="cpu", g=1.0):
+    """The package's RNN_Model: PyTorch-default draws under `seed`, every parameter then times g (g = 4 saturates the
+    gates, as forced_helper's decode nets do), or the given state dict."""
     import torch
     from neural_polar_decoder_amd.rnn import RNN_Model
     if seed is not None:
         torch.manual_seed(seed)
     net = RNN_Model("GRU", N + 1 + int(onehot), F, 1, layers, N, 0, 0, "selu", 0.0, False, out_linear_depth=1)
+    if g != 1.0:
+        with torch.no_grad():
+            for p in net.parameters():
+                p.mul_(g)
     if sd is not None:
         net.load_state_dict({k: torch.from_numpy(np.ascontiguousarray(np.asarray(v, np.float32))) for k, v in sd.items()})
     return net.to(device)
@@ -209,11 +273,17 @@ def torch_train(net, y, bits, onehot, writes, gout_step):
     return decoded.detach().double().numpy(), grads
 
 
-def e_ref(sd, F, layers, N, onehot, y, bits, writes, gout_step, g64):
-    """E_ref of a case: torch's fp32 autograd on the same inputs against the float64 gradients g64."""
+def torch_fp32(sd, F, layers, N, onehot, y, bits, writes, gout_step):
+    """torch's fp32 step loop and autograd on a case's inputs and path: (decoded, grads by name)."""
     net = build_net(F, layers, N, onehot, sd=sd).float().train()
-    _, g32 = torch_train(net, y, bits, onehot, writes, gout_step)
-    return grad_err(g32, g64)
+    return torch_train(net, y, bits, onehot, writes, gout_step)
+
+
+def e_ref(sd, F, layers, N, onehot, y, bits, writes, gout_step, g64, blockwise=False):
+    """E_ref of a case: torch's fp32 autograd on the same inputs against the float64 gradients g64 -- the largest
+    per-tensor relative error, or (blockwise) the largest per-block one."""
+    _, g32 = torch_fp32(sd, F, layers, N, onehot, y, bits, writes, gout_step)
+    return grad_err_blocks(g32, g64) if blockwise else grad_err(g32, g64)
 
 
 def load_fixture(name):
@@ -223,6 +293,45 @@ def load_fixture(name):
     for mode in ("teacher", "student"):
         fx[mode + ".g"] = {k[len(mode) + 3:]: d[k] for k in d.files if k.startswith(mode + ".g.")}
     return fx
+
+
+# ---------------------------------------------------------------------------------- the shape cases
+# tests/test_gru_train_shapes.py (CPU: the conditions the cases rest on) and tests/test_gru_train_shapes_gpu.py (the
+# kernels).  B = None: 128 CUs + 33 words, one more than a full first grid-stride trip of both recurrence kernels
+# (one workgroup per CU, 4 waves x 32 words), ending on a one-word tile; the CPU file takes 256 CUs.
+ShapeCase = collections.namedtuple("ShapeCase", "num F layers N B onehot rev student g seed why")
+SHAPE_CASES = (
+    ShapeCase(1, 32, 1, 8, 33, False, False, True, 1.0, 7201, "minimum length: one k-group of y per lane half"),
+    ShapeCase(2, 64, 2, 24, 70, True, True, False, 1.0, 7202, "odd length: 12 floats per lane half"),
+    ShapeCase(3, 64, 2, 64, 70, False, True, True, 1.0, 7203, "the quoted shape: two full mask words"),
+    ShapeCase(4, 32, 2, 128, 33, True, False, False, 1.0, 7204, "four mask words"),
+    ShapeCase(5, 64, 1, 256, 33, True, False, True, 1.0, 7205, "the limit: eight mask words, Din = 258"),
+    ShapeCase(6, 64, 2, 256, 70, False, True, True, 1.0, 7206, "the limit on the largest kernel"),
+    ShapeCase(7, 64, 2, 64, 1100, True, True, True, 1.0, 7207,
+              "split cap: NB = 70,400 (256 partials, chunk 275 -> 276, short last partial); dW_hh K = 69,300 "
+              "(chunk 272, empty last partial)"),
+    ShapeCase(8, 32, 1, 8, None, True, False, False, 1.0, 7208,
+              "second grid-stride trip of both recurrence kernels, ending on a one-word tile and on waves with no "
+              "tile; split cap with a chunk of about 1026"),
+    ShapeCase(9, 64, 2, 16, 70, True, False, True, 4.0, 7209, "saturated gates"),
+    ShapeCase(10, 32, 1, 40, 70, False, True, False, 4.0, 7210, "saturated gates, raw feed"),
+)
+
+
+def shape_id(c):
+    return f"case{c.num}-f{c.F}x{c.layers}-n{c.N}-b{c.B or 'cus'}-{'onehot' if c.onehot else 'raw'}-" \
+           f"{'rev' if c.rev else 'fwd'}-{'student' if c.student else 'teacher'}-g{c.g:g}"
+
+
+def shape_batch(c, cus=256):
+    return c.B if c.B is not None else 128 * cus + 33
+
+
+def shape_inputs(c, B):
+    """y, gt (position frame) and a random grad_out (position frame) of a shape case at batch B."""
+    y, gt = make_words(B, c.N, c.seed)
+    gout = np.random.default_rng(c.seed + 1).standard_normal((B, c.N)).astype(np.float32)
+    return y, gt, gout
 
 
 def make_words(B, N, seed):
