@@ -17,17 +17,8 @@ all: $(LIB) $(ORACLE)
 lib: $(LIB)
 oracle: $(ORACLE)
 
-# per-file extras: the SC kernel never sees NaN (finite LLRs), so fmin needs no canonicalisation
-EXTRA_npd_sc := -fno-honor-nans
-EXTRA_npd_sc_fast := -fno-honor-nans
-EXTRA_npd_scl := -fno-honor-nans
-EXTRA_npd_scl_pac := -fno-honor-nans
-EXTRA_npd_scl_wide := -fno-honor-nans
-EXTRA_npd_scl_pac_wide := -fno-honor-nans
-EXTRA_npd_scl_crc := -fno-honor-nans
-EXTRA_npd_scl_crc_pac := -fno-honor-nans
-EXTRA_npd_scl_crc_wide := -fno-honor-nans
-EXTRA_npd_scl_crc_pac_wide := -fno-honor-nans
+# per-file extras: the SC and SC-List kernels (npd_sc*) never see NaN (finite LLRs), so fmin needs no canonicalisation
+extra = $(if $(filter npd_sc%,$(1)),-fno-honor-nans,$(EXTRA_$(1)))
 # the ML/MAP epilogues read every MFMA result on the VALU: keep the accumulators in VGPRs (no v_accvgpr_read per value)
 EXTRA_npd_ml := -mllvm -amdgpu-mfma-vgpr-form=1
 # the two-tile count sweep uses more than 256 registers; its gate updates read every accumulator on the VALU as well
@@ -35,7 +26,7 @@ EXTRA_npd_gru_split16 := -mllvm -amdgpu-mfma-vgpr-form=1
 
 $(OBJDIR)/%.o: $(PKG)/csrc/%.hip $(CHDR)
 	@mkdir -p $(OBJDIR)
-	$(HIPCC) $(HIPFLAGS) $(EXTRA_$*) -c $< -o $@
+	$(HIPCC) $(HIPFLAGS) $(call extra,$*) -c $< -o $@
 
 $(LIB): $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(OBJS) -Wl,--no-undefined
@@ -51,7 +42,7 @@ $(ORACLE): oracle/npd_oracle.c oracle/npd_oracle_scl.cpp oracle/npd_oracle_lse.c
 
 asm: $(CSRC)
 	@mkdir -p build/asm
-	for f in $(CSRC); do b=$$(basename $$f .hip); $(HIPCC) $(HIPFLAGS) $$( case $$b in npd_sc*) echo -fno-honor-nans;; npd_ml|npd_gru_split16) echo -mllvm -amdgpu-mfma-vgpr-form=1;; esac ) --cuda-device-only -S -o build/asm/$$b.s $$f; done
+	$(foreach b,$(basename $(notdir $(CSRC))),$(HIPCC) $(HIPFLAGS) $(call extra,$(b)) --cuda-device-only -S -o build/asm/$(b).s $(PKG)/csrc/$(b).hip &&) true
 
 clean:
 	rm -rf build $(LIB) $(ORACLE)

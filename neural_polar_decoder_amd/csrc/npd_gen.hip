@@ -4,13 +4,10 @@
 //   npd_awgn         <- PolarCode.channel (polar.py:201-207) / PAC.channel (pac_code.py:226-231)
 //   npd_mc_generate  <- msg = 1-2*randint; x = encode(msg); y = channel(x) (run_models.py:318-323)
 //   npd_count_errors <- errors_ber / errors_bler counting (utils.py:17-51)
-#include "npd_common.hpp"
+#include "npd_sc_prim.hpp"
 
 namespace npd {
 namespace gen {
-
-__device__ __forceinline__ void lds_wr(char* lds, uint32_t byte, float v) { *reinterpret_cast<float*>(lds + byte) = v; }
-__device__ __forceinline__ float lds_rd(const char* lds, uint32_t byte) { return *reinterpret_cast<const float*>(lds + byte); }
 
 // ---------------------------------------------------------------------------------- encode (float, exact)
 // One lane per codeword; the codeword row lives in LDS (stride N+1 floats: conflict-free per-lane rows).

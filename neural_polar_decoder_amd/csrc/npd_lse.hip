@@ -22,9 +22,7 @@
 // every product opaque); exp/log/tanh are the device libm (<= 1 ulp, as is torch's CPU Sleef path),
 // so results agree with the reference to a few ulp and decisions agree except on near-zero LLRs
 // (tests/test_lse_gpu.py states the tolerance).
-#include <stdlib.h>
-
-#include "npd_common.hpp"
+#include "npd_sc_prim.hpp"
 
 namespace npd {
 namespace lse {
@@ -37,12 +35,6 @@ struct Args {
     int64_t ntiles;
     float scale;
 };
-
-__device__ __forceinline__ float rmul(float a, float b) {
-    float r = a * b;
-    asm("" : "+v"(r));
-    return r;
-}
 
 // log_sum_avoid_NaN (utils.py:295-345) evaluated elementwise.  The reference computes the "standard"
 // formula and, only if the TENSOR holds a NaN/inf, patches four index sets.  Every element of a patched

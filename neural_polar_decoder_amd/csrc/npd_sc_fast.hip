@@ -10,9 +10,8 @@
 //   * decisions of information positions are written as int8 in SLOT order (rank of the position),
 //     so msg_hat rows are contiguous bytes: the error count compares 4 slots per dword against the
 //     Philox message bits, and msg_hat leaves as coalesced 16-B stores.
-#include "npd_common.hpp"
-
-#include <cstdlib>
+#include "npd_sc_fast.hpp"
+#include "npd_sc_prim.hpp"
 
 // Tuning knobs (compile-time; defaults are the measured best on MI355X):
 #ifndef NPD_SCF_WPE
@@ -44,26 +43,6 @@ struct Args {
     uint32_t count;
     uint32_t ilv;                    // tile order: 0 = a workgroup's waves take adjacent tiles, 1 = interleaved
 };
-
-__device__ __forceinline__ float rmul(float a, float b) {
-    float r = a * b;
-    asm("" : "+v"(r));  // keep fl32(scale*y) rounded (no fma contraction), as polar.py:468
-    return r;
-}
-
-// sign(a) sign(b) min(|a|, |b|) in two VALU ops: med3(|a|, -|a|, b) = clamp(b, -|a|, |a|) has the
-// magnitude min(|a|, |b|) and the sign of b; xor in the sign of a (v_med3_f32 + v_bitop3_b32).
-// Equal in value to the reference's product form (zeros may differ only in their sign bit, which
-// no later step reads: sign(+-0) = 0, |+-0| = 0, u * (+-0) + b = b).
-__device__ __forceinline__ float f_minsum(float a, float b) {
-    const float m = __builtin_amdgcn_fmed3f(__builtin_fabsf(a), -__builtin_fabsf(a), b);
-    return bitsf(__builtin_amdgcn_bitop3_b32(fbits(m), fbits(a), 0x80000000u, 0x78));  // m ^ (a & 0x80000000)
-}
-
-__device__ __forceinline__ float sgn_bits(float x) {
-    const float s = bitsf((fbits(x) & 0x80000000u) | 0x3f800000u);
-    return (x == 0.0f) ? 0.0f : s;
-}
 
 typedef float f4 __attribute__((ext_vector_type(4)));
 typedef float f2 __attribute__((ext_vector_type(2)));
@@ -242,25 +221,6 @@ __device__ __forceinline__ void snode(Lane<N>& c, uint32_t& bad) {
 
 }  // namespace spec
 
-template <int N>
-constexpr int log2c() {
-    int n = 0;
-    while ((1 << n) < N) ++n;
-    return n;
-}
-
-template <int C>
-__device__ __forceinline__ int swz(int r) {
-    if constexpr (C >= 16) return r & 15;
-    else return (r / (16 / C)) % C;
-}
-
-// number of nonzero bytes in x
-__device__ __forceinline__ uint32_t nz_bytes(uint32_t x) {
-    const uint32_t t = ((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x;
-    return (uint32_t)__builtin_popcount(t & 0x80808080u);
-}
-
 // msg_hat of one finished tile: its rows*K floats are contiguous in HBM; decisions are int8 in slot order
 template <int N>
 __device__ __forceinline__ void store_msg(const char* lds, uint32_t kU, float* msg, int64_t row0, int rows, int K,
@@ -363,36 +323,15 @@ __device__ __forceinline__ void codeword_bits(const uint32_t (&mw)[4], const uin
             ++kk;
         }
     }
-#pragma unroll
-    for (int h = 1; h < 32 && h < N; h <<= 1) {
-        uint32_t msk = 0;
-        for (int i = 0; i < 32; ++i)
-            if (((i / h) & 1) == 0) msk |= 1u << i;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) U[w] ^= (U[w] >> h) & msk;
-    }
-#pragma unroll
-    for (int hw = 1; hw < NW; hw <<= 1)
-#pragma unroll
-        for (int w = 0; w < NW; ++w)
-            if (((w / hw) & 1) == 0) U[w] ^= U[w + hw];
+    plotkin_bits<N>(U);
 }
 
 template <int N>
 __device__ __forceinline__ void gen_llrs(float* lv, const uint32_t (&U)[(N + 31) / 32], uint64_t seed, uint32_t stream,
                                          uint64_t cw, float sigma, float scale) {
 #pragma unroll
-    for (int j = 0; j < N / 4; ++j) {
-        const u32x4 o = philox_block(seed, stream, cw, (uint32_t)j);
-        float z[4];
-        normals4(o, z);
-        const uint32_t bits = (U[(4 * j) >> 5] >> ((4 * j) & 31)) & 0xFu;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float xv = ((bits >> e) & 1u) ? -1.0f : 1.0f;
-            lv[4 * j + e] = rmul(scale, __fadd_rn(xv, __fmul_rn(sigma, z[e])));
-        }
-    }
+    for (int j = 0; j < N / 4; ++j)
+        noisy_chunk(U, seed, stream, cw, j, sigma, [&](int e, float y) { lv[4 * j + e] = rmul(scale, y); });
 }
 
 // GEN (nothing staged, ~108 VGPRs): two 8-wave workgroups per CU = 4 waves per SIMD hide the Philox /
@@ -661,11 +600,6 @@ static uint32_t tile_interleave(bool gen) {
     return v >= 0 ? (uint32_t)v : (gen ? 0u : 1u);
 }
 
-static bool spec_disabled() {
-    const char* e = getenv("NPD_SC_NOSPEC");
-    return e && e[0] == '1';
-}
-
 // eligible: Polar, 8 <= N <= 64, K <= 128 (one Philox block of message bits), y 16-B aligned
 bool sc_fast_eligible(const CodeParams& p, const void* y) {
     return !p.pac && p.N >= 8 && p.N <= 64 && p.K <= 128 && (((uintptr_t)y) & 15) == 0;
@@ -694,7 +628,7 @@ int sc_fast_run_gen(const CodeParams& p, const float* sigma, const float* llr_sc
     }
     a.count = counters ? 1u : 0u;
     a.ilv = tile_interleave(true);
-    if (!spec_disabled()) {
+    if (!env_flag("NPD_SC_NOSPEC")) {
         uint64_t m = 0;
         for (int i = 0; i < p.N; ++i)
             if ((p.frozen[i >> 5] >> (i & 31)) & 1u) m |= 1ull << i;
@@ -726,7 +660,7 @@ int sc_fast_run(const CodeParams& p, const float* y, const float* llr_scale, int
     a.count = counters ? 1u : 0u;
     a.ilv = tile_interleave(false);
     // the reference's standard codes ('polar' rate profile, K = N/2) have specialised decoders
-    if (!spec_disabled() && p.N <= 64) {
+    if (!env_flag("NPD_SC_NOSPEC") && p.N <= 64) {
         uint64_t m = 0;
         for (int i = 0; i < p.N; ++i)
             if ((p.frozen[i >> 5] >> (i & 31)) & 1u) m |= 1ull << i;

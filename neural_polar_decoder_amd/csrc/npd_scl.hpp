@@ -36,6 +36,7 @@
 #pragma once
 #include "npd_common.hpp"
 #include "npd_nth.hpp"
+#include "npd_sc_prim.hpp"
 
 namespace npd {
 namespace scl {
@@ -58,35 +59,6 @@ struct Args {
 };
 
 typedef float f4 __attribute__((ext_vector_type(4)));
-
-template <int N>
-constexpr int log2c() {
-    int n = 0;
-    while ((1 << n) < N) ++n;
-    return n;
-}
-
-template <int C>
-__device__ __forceinline__ int swz(int r) {
-    if constexpr (C >= 16) return r & 15;
-    else return (r / (16 / C)) % C;
-}
-
-__device__ __forceinline__ float rmul(float a, float b) {
-    float r = a * b;
-    asm("" : "+v"(r));  // keep the product rounded (no fma contraction into a following add)
-    return r;
-}
-
-__device__ __forceinline__ float f_minsum(float a, float b) {
-    const float m = __builtin_fminf(__builtin_fabsf(a), __builtin_fabsf(b));
-    return bitsf(fbits(m) | ((fbits(a) ^ fbits(b)) & 0x80000000u));
-}
-
-__device__ __forceinline__ float sgn_bits(float x) {
-    const float s = bitsf((fbits(x) & 0x80000000u) | 0x3f800000u);
-    return (x == 0.0f) ? 0.0f : s;
-}
 
 // value of lane (group base + T) for every lane of a G-lane group
 template <int G, int T>
@@ -436,7 +408,7 @@ __device__ __forceinline__ void node(Lane<N, G>& c, int lane) {
     } else {
         constexpr int h = 1 << (D - 1);
 #pragma unroll
-        for (int j = 0; j < h; ++j) c.lv[h + j] = f_minsum(c.lv[2 * h + j], c.lv[3 * h + j]);
+        for (int j = 0; j < h; ++j) c.lv[h + j] = f_minsum_fmin(c.lv[2 * h + j], c.lv[3 * h + j]);
         node<PAC, N, G, D - 1, S0>(c, lane);
 #pragma unroll
         for (int j = 0; j < h; ++j) c.lv[h + j] = c.beta[S0 + j] * c.lv[2 * h + j] + c.lv[3 * h + j];
@@ -820,7 +792,7 @@ __device__ __forceinline__ f4 top4(const f4* y4, float scale, int x, bool right,
     f4 o;
     if (!right) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = f_minsum(rmul(scale, u[e]), rmul(scale, v[e]));
+        for (int e = 0; e < 4; ++e) o[e] = f_minsum_fmin(rmul(scale, u[e]), rmul(scale, v[e]));
     } else {
         const uint32_t sw = BW[(rowBS + (x >> 5)) * kWave + lane], zw = BW[(rowBZ + (x >> 5)) * kWave + lane];
 #pragma unroll
@@ -876,7 +848,7 @@ __global__ __launch_bounds__(64) void scl_lds_kernel(const CodeParams p, const A
                     const f4 Bv = top4<N>(y4, a.scale, 4 * q + h2, right, BW, R::kBS, R::kBZ, lane);
                     if (!gstep) {
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) LVL(h2 - 2 + 4 * q + e) = f_minsum(A[e], Bv[e]);
+                        for (int e = 0; e < 4; ++e) LVL(h2 - 2 + 4 * q + e) = f_minsum_fmin(A[e], Bv[e]);
                     } else {
                         const int q0 = s0 + 4 * q;
                         const uint32_t sw = BWL(R::kBS + (q0 >> 5)), zw = BWL(R::kBZ + (q0 >> 5));
@@ -890,7 +862,7 @@ __global__ __launch_bounds__(64) void scl_lds_kernel(const CodeParams p, const A
                 for (int q = 0; q < h / 4; ++q) {
                     const f4 u = y4[q], v = y4[q + h / 4];
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) LVL(h - 2 + 4 * q + e) = f_minsum(rmul(a.scale, u[e]), rmul(a.scale, v[e]));
+                    for (int e = 0; e < 4; ++e) LVL(h - 2 + 4 * q + e) = f_minsum_fmin(rmul(a.scale, u[e]), rmul(a.scale, v[e]));
                 }
                 d = n - 1;
             } else {  // right child of the node of 2^(k+1) leaves starting at i - 2^k
@@ -926,14 +898,14 @@ __global__ __launch_bounds__(64) void scl_lds_kernel(const CodeParams p, const A
             }
             for (int dd = d - 1; dd >= 1; --dd) {  // left children down to level 1
                 const int h = 1 << dd;
-                for (int jj = 0; jj < h; ++jj) LVL(h - 2 + jj) = f_minsum(LVL(2 * h - 2 + jj), LVL(2 * h - 2 + h + jj));
+                for (int jj = 0; jj < h; ++jj) LVL(h - 2 + jj) = f_minsum_fmin(LVL(2 * h - 2 + jj), LVL(2 * h - 2 + h + jj));
             }
             float l;
             if (d == 0) {  // leaf i is a right child: g from level 1 with the left sibling's decision
                 const uint32_t sw = BWL(R::kBS + ((i - 1) >> 5)), zw = BWL(R::kBZ + ((i - 1) >> 5));
                 l = beta_val(sw, zw, (i - 1) & 31) * LVL(0) + LVL(1);
             } else {
-                l = f_minsum(LVL(0), LVL(1));
+                l = f_minsum_fmin(LVL(0), LVL(1));
             }
 
             // ---- leaf (polar.py:805-866)

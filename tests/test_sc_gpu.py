@@ -95,12 +95,28 @@ def test_sc_decode_vs_oracle_random(oracle, N, K):
         assert np.array_equal(leaf.cpu().numpy(), ol) and np.array_equal(hat.cpu().numpy(), oh), B
 
 
-def test_pac_vs_oracle_random(oracle):
-    pac = pac_for(128, 64)
+def _case(defaults, *vals, **more):
+    """pytest.param of vals plus the parameters added later (defaults, overridden by more).  The id is the one the
+    case had before those parameters existed, with the overrides appended: adding a parameter renames no case."""
+    extra = {**defaults, **more}
+    return pytest.param(*vals, *extra.values(), id="-".join([str(v) for v in vals] + [f"{k}{v}" for k, v in more.items()]))
+
+
+# B = 130: two full 64-word tiles and a 2-row tail (tile loop, tail clamp, uncounted tail lanes)
+@pytest.mark.parametrize("N,K,B", [(128, 64, 777), (4, 2, 130), (8, 4, 130), (16, 8, 130), (256, 128, 130)])
+def test_pac_vs_oracle_random(oracle, N, K, B):
+    """The PAC kernels with leaf LLR / u_hat outputs, and with genie decisions, at every length no golden file has."""
+    pac = pac_for(N, K)
     rng = np.random.default_rng(3)
-    y = rng.standard_normal((777, 128)).astype(np.float32)
+    y = rng.standard_normal((B, N)).astype(np.float32)
     leaf, hat, uh = pac.pac_sc_decode(t(y), 0.5)
     ol, oh, ou = oracle.pac_sc_decode(y, 0.5, pac.B)
+    assert np.array_equal(leaf.cpu().numpy(), ol)
+    assert np.array_equal(hat.cpu().numpy(), oh)
+    assert np.array_equal(uh.cpu().numpy(), ou)
+    gt = (1 - 2 * (rng.random((B, N)) < 0.5)).astype(np.float32)
+    leaf, hat, uh = pac.pac_sc_decode(t(y), 0.5, use_gt_codeword=t(gt))
+    ol, oh, ou = oracle.pac_sc_decode(y, 0.5, pac.B, gt=gt)
     assert np.array_equal(leaf.cpu().numpy(), ol)
     assert np.array_equal(hat.cpu().numpy(), oh)
     assert np.array_equal(uh.cpu().numpy(), ou)
@@ -152,10 +168,19 @@ def test_mc_generate_matches_oracle(oracle, N, K, pac):
     assert np.abs(y.cpu().numpy() - oy).max() < 2e-5
 
 
-@pytest.mark.parametrize("N,K,pac", [(64, 32, False), (32, 16, False), (128, 64, False), (256, 128, False),
-                                     (128, 64, True), (64, 22, True)])
-def test_sc_decode_mc_counters_exact(oracle, N, K, pac):
-    """Fused decode+count on GPU-generated y == oracle decode + count on the same y (bit-exact)."""
+_MC = dict(B=5000, generic=False)
+
+
+@pytest.mark.parametrize("N,K,pac,B,generic", [
+    _case(_MC, 64, 32, False), _case(_MC, 32, 16, False), _case(_MC, 128, 64, False), _case(_MC, 256, 128, False),
+    _case(_MC, 128, 64, True), _case(_MC, 64, 22, True),
+    _case(_MC, 4, 2, True, B=130), _case(_MC, 8, 4, True, B=130), _case(_MC, 16, 8, True, B=130),
+    _case(_MC, 256, 128, True, B=130), _case(_MC, 4, 2, False, B=130), _case(_MC, 8, 4, False, B=130, generic=True),
+    _case(_MC, 16, 8, False, B=130, generic=True)])
+def test_sc_decode_mc_counters_exact(oracle, monkeypatch, N, K, pac, B, generic):
+    """Fused decode+count on GPU-generated y == oracle decode + count on the same y (bit-exact).  The B = 130
+    cases reach the msg-only kernels no other case does: PAC at N = 4, 8, 16, 256, and (generic: NPD_SC_GENERIC=1,
+    read per call) the generic Polar kernel at the lengths the fast kernel otherwise takes."""
     if pac:
         code = pac_for(N, K)
         info = code.B
@@ -163,7 +188,9 @@ def test_sc_decode_mc_counters_exact(oracle, N, K, pac):
         from neural_polar_decoder_amd import reference_polar_code
         code = reference_polar_code(N, K)
         info = code.info_positions
-    B, seed, off = 5000, 42, 12345
+    if generic:
+        monkeypatch.setenv("NPD_SC_GENERIC", "1")
+    seed, off = 42, 12345
     for si, snr in enumerate([0.0, 2.0, 4.0]):
         msg, _, y = code.mc_generate(B, snr, seed, si, off)
         cnt = torch.zeros(2, dtype=torch.int64, device=DEV)
@@ -321,14 +348,22 @@ def test_specialised_8_4_and_high_snr_vs_oracle(oracle):
             assert np.array_equal(code.sc_decode_msg(y, snr).cpu().numpy(), oh), (N, snr)
 
 
-@pytest.mark.parametrize("N,K,B", [(64, 32, 100_003), (32, 16, 5000), (16, 8, 777), (64, 22, 3001), (8, 4, 4099),
-                                   (4, 2, 1000), (128, 64, 20_001), (256, 128, 3333), (256, 200, 700)])
-def test_fused_mc_sweep_equals_generate_then_decode(N, K, B):
+_FUSED = dict(generic=False)
+
+
+@pytest.mark.parametrize("N,K,B,generic", [
+    _case(_FUSED, 64, 32, 100_003), _case(_FUSED, 32, 16, 5000), _case(_FUSED, 16, 8, 777), _case(_FUSED, 64, 22, 3001),
+    _case(_FUSED, 8, 4, 4099), _case(_FUSED, 4, 2, 1000), _case(_FUSED, 128, 64, 20_001), _case(_FUSED, 256, 128, 3333),
+    _case(_FUSED, 256, 200, 700), _case(_FUSED, 8, 4, 130, generic=True), _case(_FUSED, 16, 8, 130, generic=True),
+    _case(_FUSED, 32, 16, 130, generic=True), _case(_FUSED, 64, 32, 130, generic=True)])
+def test_fused_mc_sweep_equals_generate_then_decode(oracle, monkeypatch, N, K, B, generic):
     """npd_sc_mc_sweep_fused (message -> codeword -> AWGN generated inside the decode kernel, y never
     stored) == npd_mc_generate + npd_sc_decode_mc_sweep: identical msg_hat and counters at every SNR,
     including 25 dB, where the specialised decoder's closed-form subtrees fall back to step-by-step SC
     (regenerated received words).  N <= 64: the fast kernel's GEN mode; N = 4, 128, 256: the generic
-    kernel's (K = 200 > 128: two Philox message blocks)."""
+    kernel's (K = 200 > 128: two Philox message blocks).  generic (NPD_SC_GENERIC=1, read per call): the generic
+    kernel's GEN mode and its msg-only streaming mode at the lengths the fast kernel otherwise takes, three SNR
+    points, and both equal to the oracle's decode and count of the generated words."""
     from neural_polar_decoder_amd import PolarCode, reference_polar_code
     from neural_polar_decoder_amd.codes import polar_info_positions
     if K in (22, 200):
@@ -337,8 +372,10 @@ def test_fused_mc_sweep_equals_generate_then_decode(N, K, B):
     else:
         code = reference_polar_code(N, K)
     assert code.fused_mc_supported() == (N <= 128)  # N = 256: the driver generates y (faster), the ABI still fuses
-    snrs = [-1.0, 1.5, 3.0, 25.0]
+    snrs = [-1.0, 1.5, 3.0] if generic else [-1.0, 1.5, 3.0, 25.0]
     seed, off, si0 = 13, 12345, 2
+    if generic:
+        monkeypatch.setenv("NPD_SC_GENERIC", "1")
     y = torch.empty(len(snrs), B, N, device=DEV)
     for i, s in enumerate(snrs):
         code.mc_generate(B, s, seed, si0 + i, off, out=y[i], want_msg=False)
@@ -350,14 +387,28 @@ def test_fused_mc_sweep_equals_generate_then_decode(N, K, B):
     code.sc_mc_sweep_fused(B, snrs, seed, off, c2, msg_hat=h2, snr_index0=si0)
     assert torch.equal(h1, h2)
     assert torch.equal(c1, c2), (c1.tolist(), c2.tolist())
+    if generic:
+        _oracle_sweep_check(oracle, code, code.info_positions, False, y, snrs, seed, off, h2, c2)
+
+
+def _oracle_sweep_check(oracle, code, info, pac, y, snrs, seed, off, hat, cnt):
+    """msg_hat (S, B, K) and counters (S, 2) of a sweep over the received words y (S, B, N) == the oracle's"""
+    msg = oracle.gen_msg(y.shape[1], len(info), seed, off)
+    for i, s in enumerate(snrs):
+        yh = y[i].cpu().numpy()
+        oh = oracle.pac_sc_decode(yh, s, info)[1] if pac else oracle.sc_decode(yh, s, info)[1]
+        assert np.array_equal(hat[i].cpu().numpy(), oh), s
+        assert cnt[i].tolist() == list(oracle.count_errors(msg, oh)), s
 
 
 @pytest.mark.parametrize("N,K,B,nospec", [(128, 64, 50_001, False), (128, 64, 3001, True), (64, 22, 4097, False),
-                                          (32, 16, 999, False), (256, 128, 2000, False)])
-def test_pac_fused_mc_sweep_equals_generate_then_decode(N, K, B, nospec, monkeypatch):
+                                          (32, 16, 999, False), (256, 128, 2000, False), (4, 2, 130, False),
+                                          (8, 4, 130, False), (16, 8, 130, False)])
+def test_pac_fused_mc_sweep_equals_generate_then_decode(oracle, N, K, B, nospec, monkeypatch):
     """PAC: the generic kernel's GEN mode (msg -> v -> convolution -> Plotkin -> AWGN in registers, PAC SC,
     counts) == npd_mc_generate + npd_sc_decode_mc per SNR point: identical v_hat[:, B] and counters.
-    PAC(128,64) 'RM' runs the compile-time frozen-set kernel; nospec forces the run-time frozen set."""
+    PAC(128,64) 'RM' runs the compile-time frozen-set kernel; nospec forces the run-time frozen set.  The B = 130
+    cases (N = 4, 8, 16: kernels no other case reaches) run three SNR points and are also held to the oracle."""
     import argparse
     from neural_polar_decoder_amd import PAC
     if nospec:
@@ -365,18 +416,23 @@ def test_pac_fused_mc_sweep_equals_generate_then_decode(N, K, B, nospec, monkeyp
     code = PAC(argparse.Namespace(target_K=K), N, K, 91)
     # the C ABI fuses every N; the Monte-Carlo driver takes the fused path up to N = 128 (N = 256 spills)
     assert code.fused_mc_supported() == (N <= 128)
-    snrs = [-1.0, 1.0, 2.5, 25.0]
+    snrs = [-1.0, 1.0, 2.5] if B == 130 else [-1.0, 1.0, 2.5, 25.0]
     seed, off, si0 = 29, 777, 1
     c1 = torch.zeros(len(snrs), 2, dtype=torch.int64, device=DEV)
     h1 = torch.empty(len(snrs), B, K, device=DEV)
+    ys = []
     for i, s in enumerate(snrs):
         _, _, y = code.mc_generate(B, s, seed, si0 + i, off, device=DEV, want_msg=False)
         code.sc_decode_mc(y, s, seed, off, c1[i], msg_hat=h1[i])
+        if B == 130:
+            ys.append(y)
     c2 = torch.zeros(len(snrs), 2, dtype=torch.int64, device=DEV)
     h2 = torch.empty(len(snrs), B, K, device=DEV)
     code.sc_mc_sweep_fused(B, snrs, seed, off, c2, msg_hat=h2, snr_index0=si0)
     assert torch.equal(h1, h2)
     assert torch.equal(c1, c2), (c1.tolist(), c2.tolist())
+    if B == 130:
+        _oracle_sweep_check(oracle, code, code.B, True, torch.stack(ys), snrs, seed, off, h2, c2)
 
 
 def test_fused_mc_argument_checks():
