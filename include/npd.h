@@ -529,6 +529,49 @@ int npd_conv_forward_ex(const npd_conv* conv, const float* y, float* logits, flo
 int npd_conv_forward_tap(const npd_conv* conv, const float* y, float* logits, float* decoded, int tap, float* tap_out,
                          void* workspace, int64_t B, void* stream);
 
+/* ---------------------------------------------------------------------------------- conv model training */
+typedef struct npd_conv_train npd_conv_train; /* the plan of one (N, embed): the device buffers of the weight images */
+/*
+ * convNet.forward in training mode (models.py:742-767), differentiable, fp32 (exact fp32 FMA chains on the fp32 MFMA;
+ * the fp16x3 split has no training kernels).  N a multiple of 64 in [64, 1024], embed a multiple of 16 in [16, 512]
+ * (anything else NPD_EINVAL); embed > 448 is refused with NPD_ENOTSUP (layer 8's dX slab would pass 160 KB of LDS).
+ * The plan holds no weights: every call takes all parameters as one flat DEVICE fp32 vector in npd_conv_create's
+ * order (per conv layer w then b, then 3 x (w, b) Linear, then the LayerNorm g, b; zeros for absent biases) and packs
+ * the images it reads from it on the device, so a call after an optimiser step sees the new weights with no host copy
+ * and no synchronisation.  One plan serves one stream at a time.  npd_conv_train_destroy(NULL) is NPD_EINVAL.
+ */
+int npd_conv_train_create(int N, int embed, npd_conv_train** out);
+int npd_conv_train_destroy(npd_conv_train* plan);
+/*
+ * Sizes (in floats) of the two caller-owned device buffers of a batch of B words (0 <= B <= 2^22), H = embed / 2:
+ *   saved   (forward writes, backward reads): per conv layer the pre-activation z and the output, 2 B N (8 H + 2 embed);
+ *           FC0 and FC1 z and output, 2 B (4 N + N); the dropout-scaled FC2 output, B N; the per-word mean and rstd,
+ *           2 B rounded up to 4.
+ *   scratch (backward's own): two gradient buffers of B N embed, two skip-gradient buffers of B N H, B N for the
+ *           LayerNorm weight's per-word products, and the partial sums of the largest weight-gradient reduction (at
+ *           most 2^26 floats: up to 4096 partials of a conv weight, about 1024 workgroups' worth of a Linear weight).
+ * Both must be 16-byte aligned.  `saved` begins with, for conv layer i = 0 .. 9 in turn, z_i and then the layer's output
+ * (after GELU and the residual), each (B, N, cout_i) with channels contiguous -- layer 5's output is convNet.forward's
+ * input4; the rest of the layout is the library's.
+ */
+int npd_conv_train_workspace(const npd_conv_train* plan, int64_t B, int64_t* saved_floats, int64_t* scratch_floats);
+/*
+ * logits (B, N) = LayerNorm(drop_mult * FC2(...)), eps 1e-6.  y (B, N) device fp32, 16-byte aligned; drop_mult (B, N)
+ * device fp32 of 0 or 1 / (1 - p), NULL = no dropout.  Launches on `stream`, no allocation, no synchronisation; words
+ * beyond 32768 go to further launches of the conv kernels inside the call.  B = 0 returns NPD_OK with no launch.
+ */
+int npd_conv_train_forward(npd_conv_train* plan, const float* weights_dev, const float* y,
+                           const float* drop_mult_or_null, float* logits, float* saved, int64_t B, void* stream);
+/*
+ * Backward of the forward that filled `saved` (same weights_dev, y, drop_mult, B): grad_weights_dev (flat, the weights'
+ * order and length) is OVERWRITTEN with the gradient of sum(grad_logits * logits).  Every weight gradient is reduced
+ * into per-workgroup partial sums that one kernel adds in a fixed order (no floating-point atomics: equal calls return
+ * equal bits).  B = 0 zeroes the gradient.
+ */
+int npd_conv_train_backward(npd_conv_train* plan, const float* weights_dev, const float* y,
+                            const float* drop_mult_or_null, const float* grad_logits, const float* saved, float* scratch,
+                            float* grad_weights_dev, int64_t B, void* stream);
+
 /* ---------------------------------------------------------------------------------- GPT transformer */
 /*
  * XFormerEndToEndGPT.decode (models.py:398-423; run_models.py:338): at every information position i the whole

@@ -93,6 +93,12 @@ SIGNATURES = [
     ("npd_conv_forward_ex", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
     ("npd_conv_forward_tap", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_i64,
                                      c_void_p]),
+    ("npd_conv_train_create", c_int, [c_int, c_int, ctypes.POINTER(c_void_p)]),
+    ("npd_conv_train_destroy", c_int, [c_void_p]),
+    ("npd_conv_train_workspace", c_int, [c_void_p, c_i64, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
+    ("npd_conv_train_forward", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
+    ("npd_conv_train_backward", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_i64, c_void_p]),
     ("npd_gpt_create", c_int, [c_int, c_int, c_int, c_int, c_void_p, c_i64, ctypes.POINTER(c_void_p)]),
     ("npd_gpt_destroy", c_int, [c_void_p]),
     ("npd_gpt_workspace_bytes", c_i64, [c_void_p, c_i64]),

@@ -137,9 +137,90 @@ class convNet(nn.Module):
             return _lib.home(lg, noisy_enc), _lib.home(dec, noisy_enc), _lib.home(in4, noisy_enc)
         return _lib.home(lg, noisy_enc), _lib.home(dec, noisy_enc)
 
+    # ------------------------------------------------------------------ training (models.py:742-767, run_models.py:826-915)
+    def _convs(self):
+        return [self.layers1[0], self.layers1[2], self.layers2[0], self.layers2[2], self.layers3[0], self.layers3[2],
+                self.layers4[0], self.layers4[2], self.layers5[0], self.layers5[2]]
+
+    def train_reason(self, y=None):
+        """Why forward() in training mode refuses this net (None: it runs on the fused training kernels,
+        npd_conv_train_forward / _backward) -- checked before any GPU call."""
+        if self.precision != "fp32":
+            return f"fused conv training runs fp32; the fp16x3 split is a follow-up, got precision {self.precision!r}"
+        if next(self.parameters()).device.type != "cuda":
+            return "fused conv training needs the net on the GPU: libnpd has no CPU path"
+        if y is not None and getattr(y, "requires_grad", False):
+            return "fused conv training returns no gradient for y: y.requires_grad must be False"
+        n, e = self.output_len, self.hidden_dim
+        if not (64 <= n <= 1024 and n % 64 == 0) or self.input_len != n:
+            return f"fused conv training needs N = max_len a multiple of 64 in [64, 1024], got N {n}, max_len {self.input_len}"
+        if not (16 <= e <= 448 and e % 16 == 0):
+            return f"fused conv training needs embed_dim a multiple of 16 in [16, 448], got {e}"
+        return None
+
+    def train_supported(self, y=None) -> bool:
+        """True when forward() in training mode runs on the fused training kernels (no GPU call)."""
+        return self.train_reason(y) is None
+
+    def train_logits(self, noisy_enc, drop_mult=None, want_input4=False):
+        """Training-mode logits (B, N) with a grad_fn: one fused forward now, the fused backward when .backward() runs.
+        With ``want_input4`` also a detached (B, embed/2, N) copy of the activation after layers3 + residual.
+        ``drop_mult`` (B, N) of 0 or 1 / (1 - p) replaces the Dropout layer's own draw; None draws it from torch's
+        generator on the net's device as bernoulli(1 - p) / (1 - p) when ``self.dropout.p > 0`` -- the same distribution
+        as nn.Dropout, not its random stream bit for bit."""
+        why = self.train_reason(noisy_enc)
+        if why is not None:
+            raise _lib.NpdError(why)
+        dev = next(self.parameters()).device
+        y = _lib.f32c(_lib.stage(noisy_enc.detach(), "noisy_enc", dev))
+        if y.dim() != 2 or y.shape[1] != self.output_len:
+            raise ValueError(f"noisy_enc must be (batch, {self.output_len}), got {tuple(y.shape)}")
+        if y.data_ptr() % 16:
+            y = y.clone()
+        B, p = y.shape[0], float(self.dropout.p)
+        if drop_mult is not None:
+            drop_mult = _lib.f32c(_lib.stage(drop_mult.detach(), "drop_mult", dev))
+            if drop_mult.shape != y.shape:
+                raise ValueError(f"drop_mult must be {tuple(y.shape)}, got {tuple(drop_mult.shape)}")
+        elif p > 0.0:
+            if p >= 1.0:
+                drop_mult = torch.zeros_like(y)
+            else:
+                drop_mult = torch.bernoulli(torch.full_like(y, 1.0 - p)) / (1.0 - p)
+        if B == 0:
+            lg = torch.zeros(0, self.output_len, device=dev) + 0.0 * sum(q.sum() for q in self.parameters())
+            return (lg, torch.zeros(0, self.hidden_dim // 2, self.output_len, device=dev)) if want_input4 else lg
+        params, present = [], []
+        for c in self._convs():
+            params.append(c.weight)
+            present.append(True)
+            if c.bias is None:  # dont_use_bias: zeros in the flat vector, no gradient back
+                params.append(torch.zeros(c.out_channels, dtype=torch.float32, device=dev))
+                present.append(False)
+            else:
+                params.append(c.bias)
+                present.append(True)
+        for li in (0, 2, 4):
+            params += [self.layersFin[li].weight, self.layersFin[li].bias]
+        params += [self.layer_norm.weight, self.layer_norm.bias]
+        present += [True] * 8
+        plan = _conv_train_plan(dev, self.output_len, self.hidden_dim)
+        lg, in4 = _ConvTrainFn.apply(plan, y, drop_mult, tuple(present), want_input4, *params)
+        return (lg, in4) if want_input4 else lg
+
     def forward(self, noisy_enc, mask, trg_seq, device):
         """models.py:742-767: returns (output, decoded_msg_bits, out_mask, logits, input4), input4 being the
-        (B, embed/2, N) activation after layers3 + residual, written out by the fused forward on request."""
+        (B, embed/2, N) activation after layers3 + residual, written out by the fused forward on request.
+
+        In training mode logits (B, N, 1) carries the fused training kernels' grad_fn (train_logits: weights read from
+        the device on every call, dropout drawn in Python), output and decoded_msg_bits are derived from it by torch
+        ops, and input4 is DETACHED: a copy of the activation the forward kept for its backward, with no gradient (the
+        reference's active losses never use it)."""
+        if self.training:
+            lg, in4 = self.train_logits(noisy_enc, want_input4=True)
+            logits = _lib.home(lg, noisy_enc).unsqueeze(-1)
+            out = torch.sigmoid(logits)
+            return torch.cat((1 - out, out), -1), logits.detach().sign(), mask, logits, _lib.home(in4, noisy_enc)
         lg, dec, in4 = self.logits(noisy_enc, want_input4=True)
         logits = lg.unsqueeze(-1)
         out = torch.sigmoid(logits)
@@ -149,6 +230,94 @@ class convNet(nn.Module):
         """models.py:769-772: (decoded_msg_bits (B,N,1), mask)."""
         _, dec = self.logits(noisy_enc)
         return dec.unsqueeze(-1), mask
+
+
+class _ConvTrainPlan:
+    """npd_conv_train handle of one (N, embed): the kernels' device image buffers, no weights."""
+
+    def __init__(self, N, embed):
+        out = ctypes.c_void_p()
+        _lib.check(_lib.load().npd_conv_train_create(int(N), int(embed), ctypes.byref(out)), "npd_conv_train_create")
+        self.h = out
+
+    def workspace(self, B):
+        sv, sc = ctypes.c_int64(), ctypes.c_int64()
+        _lib.check(_lib.load().npd_conv_train_workspace(self.h, int(B), ctypes.byref(sv), ctypes.byref(sc)),
+                   "npd_conv_train_workspace")
+        return sv.value, sc.value
+
+    def __del__(self):
+        try:
+            if self.h:
+                _lib.load().npd_conv_train_destroy(self.h)
+        except Exception:
+            pass
+
+
+_CONV_TRAIN_PLANS = {}
+
+
+def _conv_train_plan(device, N, embed):
+    """One plan per (device, N, embed); the weights are passed per call, so nothing is keyed on them."""
+    key = (str(device), int(N), int(embed))
+    plan = _CONV_TRAIN_PLANS.get(key)
+    if plan is None:
+        with torch.cuda.device(device):
+            plan = _CONV_TRAIN_PLANS[key] = _ConvTrainPlan(N, embed)
+    return plan
+
+
+class _ConvTrainFn(torch.autograd.Function):
+    """(logits, input4) = npd_conv_train_forward(flat weights, y, drop_mult); backward = npd_conv_train_backward:
+    per-parameter views of the flat gradient.
+
+    The parameters (and y) are kept with ctx.save_for_backward: the backward packs its transposed images from the
+    weights of the forward, so an in-place change of a parameter between forward and backward (an optimiser step
+    before .backward()) raises through torch's version counter instead of mixing two sets of weights.  The plan's
+    images are rewritten by every call, which is why the backward packs its own: two forwards may precede one backward
+    on a shared plan."""
+
+    @staticmethod
+    def forward(ctx, plan, y, drop, present, want_input4, *params):
+        dev = y.device
+        B, N = y.shape
+        flat = torch.cat([p.detach().reshape(-1) for p in params]).to(torch.float32).contiguous()
+        n_saved, n_scratch = plan.workspace(B)
+        saved = torch.empty(n_saved, dtype=torch.float32, device=dev)
+        lg = torch.empty(B, N, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().npd_conv_train_forward(plan.h, _lib.ptr(flat), _lib.ptr(y), _lib.ptr(drop), _lib.ptr(lg),
+                                                          _lib.ptr(saved), B, _lib.stream_of(dev)),
+                       "npd_conv_train_forward")
+        ctx.save_for_backward(y, *params)
+        ctx.plan, ctx.saved_ws, ctx.n_scratch, ctx.drop, ctx.present = plan, saved, n_scratch, drop, present
+        # include/npd.h: `saved` starts with z and the output of each conv layer; layer 5's output is input4
+        H = params[0].shape[0]
+        in4 = saved[11 * B * N * H:12 * B * N * H].view(B, N, H).permute(0, 2, 1).contiguous() if want_input4 \
+            else torch.empty(0, device=dev)
+        ctx.mark_non_differentiable(in4)
+        return lg, in4
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout, _gin4):
+        y, *params = ctx.saved_tensors  # raises if a parameter was changed in place since the forward
+        plan, dev = ctx.plan, y.device
+        flat = torch.cat([p.detach().reshape(-1) for p in params]).to(torch.float32).contiguous()
+        g = gout.to(torch.float32).contiguous()
+        scratch = torch.empty(ctx.n_scratch, dtype=torch.float32, device=dev)
+        gflat = torch.empty_like(flat)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().npd_conv_train_backward(plan.h, _lib.ptr(flat), _lib.ptr(y), _lib.ptr(ctx.drop),
+                                                           _lib.ptr(g), _lib.ptr(ctx.saved_ws), _lib.ptr(scratch),
+                                                           _lib.ptr(gflat), y.shape[0], _lib.stream_of(dev)),
+                       "npd_conv_train_backward")
+        grads, off = [], 0
+        for p, has in zip(params, ctx.present):
+            n = p.numel()
+            grads.append(gflat[off:off + n].view(p.shape) if has else None)
+            off += n
+        return (None, None, None, None, None) + tuple(grads)
 
 
 # ------------------------------------------------------------------------------------ GPT transformer
